@@ -13,8 +13,11 @@ independently seeded models batched through the native engine; the reported valu
 whole-job aggregate model-epochs per second (weak scaling: fixed work per GPU), timed between
 barriers + device synchronisations, max over ranks.
 
-Ensemble (``ensemble9`` in the output line, measured end to end, not extrapolated): the real
-driver path `parallel.ensemble.run_ensemble` -- rank 0 generates the panel and RCCL-broadcasts
+A plain run sets up, warms up, times the ``--steps`` epochs, writes ``--dump-outputs`` and prints
+the result line; everything else the benchmark measures runs only with ``--full``.
+
+Ensemble (``--full``; ``ensemble9`` in the output line, measured end to end, not extrapolated): the
+real driver path `parallel.ensemble.run_ensemble` -- rank 0 generates the panel and RCCL-broadcasts
 it, seeds 0..8 are sharded over the ranks and batched per rank into one engine (engine build,
 panel compaction, hipGraph capture, the full 256 / 64 / 1024 schedule, final evaluation), the
 best-Sharpe weights are all-gathered and the ensemble Sharpe is computed. The reference trains
@@ -22,6 +25,8 @@ the 9 seeds serially (`/root/reference/notebooks/demo_full.ipynb:1217-1246`).
 
 Launch (the driver's two forms are equivalent):
     python bench.py --gpus N [--steps K --warmup W]          # spawns N ranks itself
+    python bench.py --gpus N --full                          # ... plus the 9-model ensemble
+    python bench.py --gpus 1 --dump-outputs DIR              # ... plus DIR/<name>.npy of the last step
     torchrun --nproc-per-node N bench.py --gpus N ...        # one rank per GPU from the env
 """
 from __future__ import annotations
@@ -74,7 +79,10 @@ def make_panel(seed: int = 0, device: str = "cpu", T=None, N=None, F=None, M=Non
 
 
 def schedule_split(k: int):
-    """Split k epochs into the 256:64:1024 phase proportion (each >= 1 when k >= 3)."""
+    """Split k epochs into the 256:64:1024 phase proportion (each >= 1 when k >= 3; the sum is
+    always k: one or two epochs go to phase 3, then phase 1)."""
+    if k < 3:
+        return max(0, k - 1), 0, min(max(k, 0), 1)
     n1 = max(1, round(k * 256 / 1344))
     n2 = max(1, round(k * 64 / 1344))
     n3 = max(1, k - n1 - n2)
@@ -186,6 +194,26 @@ def measure_ensemble(d, cfg, pc, seed_panel: int = 0):
     }
 
 
+def dump_outputs(out_dir: str, eng, n_models: int, steps: int):
+    """``--dump-outputs``: what a caller of the timed path holds after its last step, as float32
+    ``<name>.npy``: ``params`` [G, P] (every model's flat parameters after the last Adam update),
+    ``history_train`` [G, steps, columns] (the timed epochs' phase, train losses, train Sharpe,
+    gradient norm and best-so-far trackers) and ``history_eval`` [G, phase-1 and phase-3 steps,
+    columns] (their valid / test losses, Sharpe ratios and return statistics; phase 2 runs no
+    evaluation). Columns in the order of ``engine.runner.HIST``; every stored element is one the
+    run computed, so a NaN in a dump is a NaN of the run."""
+    from deeplearninginassetpricing_paperreplication_amd.engine.runner import HIST
+    os.makedirs(out_dir, exist_ok=True)
+    params = np.stack([np.asarray(eng.params(g), dtype=np.float32) for g in range(n_models)])
+    hist = np.stack([np.asarray(eng.history_rows(g), dtype=np.float32)[-steps:] for g in range(n_models)])
+    ev = sorted(c for k, c in HIST.items() if k.startswith(("valid_", "test_")))
+    tr = sorted(c for k, c in HIST.items() if c not in ev)
+    evaluated = hist[0, :, HIST["phase"]] != 2
+    np.save(os.path.join(out_dir, "params.npy"), params)
+    np.save(os.path.join(out_dir, "history_train.npy"), np.ascontiguousarray(hist[:, :, tr]))
+    np.save(os.path.join(out_dir, "history_eval.npy"), np.ascontiguousarray(hist[:, evaluated][:, :, ev]))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -195,9 +223,18 @@ def main():
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--config", choices=["real", "scaled"], default="real",
                     help="real: BASELINE config 2 (600x3000x46); scaled: config 5 (600x30000x512)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the end-to-end 9-model "
+                         "ensemble wall-clock (ensemble9 in the result line)")
     ap.add_argument("--no-ensemble9", dest="ensemble9", action="store_false",
-                    help="skip the end-to-end 9-model ensemble wall-clock reported next to the metric")
+                    help="with --full: skip the end-to-end 9-model ensemble wall-clock")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step (the trained parameters and "
+                         "the history rows of the timed epochs, per model of rank 0's GPU) as DIR/<name>.npy")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    a.ensemble9 = a.ensemble9 and a.full
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
         sys.exit(spawn_ranks(a.gpus))
     pc = SCALED if a.config == "scaled" else BENCH
@@ -258,8 +295,9 @@ def main():
     t0 = time.perf_counter()
     evs[0].record(est)
     for i, (ph, k) in enumerate(((1, n1), (2, n2), (3, n3))):
-        eng.eng.begin_phase(ph)
-        eng.run(ph, k, 1e-3, 64, 1.0, use_graph)
+        if k:
+            eng.eng.begin_phase(ph)
+            eng.run(ph, k, 1e-3, 64, 1.0, use_graph)
         evs[i + 1].record(est)
     t_enq = time.perf_counter() - t0      # host time to enqueue the timed region (vs dt: host-bound?)
     launch_us = float(eng.eng.fused_info().get("host_launch_us_per_epoch", 0.0))
@@ -267,8 +305,10 @@ def main():
     torch.cuda.synchronize()
     comm.barrier(d)
     dt = time.perf_counter() - t0
-    phase_t = [evs[i].elapsed_time(evs[i + 1]) / 1e3 / k for i, k in enumerate((n1, n2, n3))]
+    phase_t = [evs[i].elapsed_time(evs[i + 1]) / 1e3 / k if k else 0.0 for i, k in enumerate((n1, n2, n3))]
     hist = eng.history_rows(0)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, eng, G, n1 + n2 + n3)
     finite = bool(np.isfinite(hist[:, 1]).all())
     # spin waits of the fused LSTM + tower forward that gave up (0 = every published period was
     # waited for; anything else means results of that launch are invalid)

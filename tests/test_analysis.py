@@ -1,5 +1,4 @@
 """Ensemble evaluator / plots / downloader vs the reference tools."""
-import importlib
 import os
 import subprocess
 import sys
@@ -8,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+import golden_cases as gc
 from deeplearninginassetpricing_paperreplication_amd.analysis import ensemble as ens
 from deeplearninginassetpricing_paperreplication_amd.analysis import plots
 from deeplearninginassetpricing_paperreplication_amd.analysis import portfolio as pf
@@ -43,17 +43,19 @@ def test_renormalize_matches_loop():
     np.testing.assert_allclose(pf.renormalize(w, m), ref, rtol=1e-6)
 
 
-def test_evaluate_ensemble_matches_reference(reference_src, shipped_data, two_checkpoints, capsys):
-    ref = importlib.import_module("ref_src.evaluate_ensemble")
-    a = ref.evaluate_ensemble(two_checkpoints, shipped_data)
-    b = ens.evaluate_ensemble(two_checkpoints, shipped_data, verbose=False)
+def test_evaluate_ensemble_matches_reference(shipped_data, capsys):
+    """The evaluator on two recorded checkpoints of this package's CPU trainer (seeds 1 and 2,
+    ``tests/golden/ensemble_ckpt``) against the reference evaluator's recorded result on them."""
+    a = gc.load_json("ensemble_eval.json")
+    ckpts = [gc.path(os.path.join("ensemble_ckpt", f"m{seed}")) for seed in (1, 2)]
+    b = ens.evaluate_ensemble(ckpts, shipped_data, verbose=False)
     capsys.readouterr()
     for k in ("train_sharpe", "valid_sharpe", "test_sharpe"):
         assert b[k] == pytest.approx(a[k], rel=1e-5, abs=1e-7), k
     np.testing.assert_allclose(b["individual_sharpes"], a["individual_sharpes"], rtol=1e-5)
 
 
-def test_summary_statistics_match_reference_table(reference_src, shipped_data, two_checkpoints):
+def test_summary_statistics_match_reference_table(shipped_data, two_checkpoints):
     p = plots._Panel(two_checkpoints, shipped_data)
     f = p.ensemble_factor("test").astype(np.float64)
     s = pf.sdf_statistics(f)

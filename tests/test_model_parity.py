@@ -1,129 +1,121 @@
-"""Golden tests of the PyTorch (CPU) model path against the reference modules
-(`/root/reference/src/model.py`), identical state_dicts, dropout off."""
-import importlib
-
+"""Golden tests of the PyTorch (CPU) model path against the reference modules (the reference's
+``src/model.py``), identical state_dicts, dropout off. The reference's outputs on these inputs
+are recorded in ``tests/golden/model_parity.*`` (``tools/record_golden.py``)."""
 import numpy as np
 import pytest
 import torch
 
+import golden_cases as gc
 from deeplearninginassetpricing_paperreplication_amd.config import default_cli_config
-from deeplearninginassetpricing_paperreplication_amd.data.synthetic import generate_panel_fast
 from deeplearninginassetpricing_paperreplication_amd.models.gan import AssetPricingGAN, SimpleSDF
 
-CONFIGS = [
-    dict(),
-    dict(hidden_dim=[32], rnn_dim=[2, 3], num_moments=4),
-    dict(hidden_dim=[64, 48, 32], hidden_dim_moment=[16], num_moments=12),
-    dict(use_lstm=False),
-]
+CONFIGS = gc.MODEL_CONFIGS
+_batch = gc.model_batch
 
 
-def _batch(T=24, N=60, F=10, M=5, seed=0):
-    ret, feats, mask, mac = generate_panel_fast(T, N, F, M, seed=seed)
-    mac = (mac - mac.mean(0)) / (mac.std(0, unbiased=False) + 1e-8)
-    return mac, feats, ret, mask
+@pytest.fixture(scope="module")
+def golden():
+    """(arrays, metadata) recorded from the reference; read once, never modified."""
+    return gc.load_npz("model_parity.npz"), gc.load_json("model_parity.json")
 
 
-def _pair(reference_src, cfg_kw, residual=0.0, weighted=True):
-    ref_model = importlib.import_module("ref_src.model")
-    cfg = default_cli_config(5, 10, dropout=0.0, **cfg_kw)
-    cfg["residual_loss_factor"] = residual
-    cfg["weighted_loss"] = weighted
+def _ours(cfg_kw, residual=0.0, weighted=True):
     torch.manual_seed(3)
-    ref = ref_model.AssetPricingGAN(cfg)
-    torch.manual_seed(3)
-    ours = AssetPricingGAN(cfg)
-    return ref, ours, cfg
+    return AssetPricingGAN(gc.model_config(cfg_kw, residual, weighted))
 
 
 @pytest.mark.parametrize("cfg_kw", CONFIGS)
-def test_same_init_and_state_dict_layout(reference_src, cfg_kw):
-    ref, ours, _ = _pair(reference_src, cfg_kw)
-    rs, os_ = ref.state_dict(), ours.state_dict()
-    assert list(rs.keys()) == list(os_.keys())
-    for k in rs:
-        assert rs[k].shape == os_[k].shape and rs[k].dtype == os_[k].dtype
-        assert torch.equal(rs[k], os_[k]), k          # same construction order -> same init
+def test_same_init_and_state_dict_layout(golden, cfg_kw):
+    arrs, meta = golden
+    ci = CONFIGS.index(cfg_kw)
+    os_ = _ours(cfg_kw).state_dict()
+    assert meta["init_keys"][ci] == list(os_.keys())
+    for k in os_:
+        rs = gc.tensor(arrs[f"init/{ci}/{k}"])
+        assert rs.shape == os_[k].shape and rs.dtype == os_[k].dtype
+        assert torch.equal(rs, os_[k]), k          # same construction order -> same init
 
 
 @pytest.mark.parametrize("cfg_kw", CONFIGS)
 @pytest.mark.parametrize("phase", ["unconditional", "moment", "conditional"])
-def test_forward_outputs_match(reference_src, cfg_kw, phase):
-    ref, ours, _ = _pair(reference_src, cfg_kw)
-    ref.eval(); ours.eval()
+def test_forward_outputs_match(golden, cfg_kw, phase):
+    arrs, meta = golden
+    ci = CONFIGS.index(cfg_kw)
+    ours = _ours(cfg_kw)
+    ours.eval()
     mac, feats, ret, mask = _batch()
     with torch.no_grad():
-        a = ref(mac, feats, ret, mask, phase=phase)
         b = ours(mac, feats, ret, mask, phase=phase)
-    for k in ("weights", "loss", "loss_unconditional", "loss_conditional", "sharpe", "portfolio_returns",
-              "moments"):
-        torch.testing.assert_close(b[k], a[k], rtol=2e-5, atol=1e-7, msg=k)
-    assert set(a.keys()) == set(b.keys())
+    for k in gc.FORWARD_KEYS:
+        torch.testing.assert_close(b[k], gc.tensor(arrs[f"fwd/{ci}/{phase}/{k}"]), rtol=2e-5, atol=1e-7, msg=lambda m, k=k: f"{k}: {m}")
+    assert set(meta["forward_keys"][f"{ci}/{phase}"]) == set(b.keys())
 
 
 @pytest.mark.parametrize("phase", ["unconditional", "moment", "conditional"])
 @pytest.mark.parametrize("residual,weighted", [(0.0, True), (0.5, True), (0.0, False)])
-def test_gradients_match(reference_src, phase, residual, weighted):
-    ref, ours, _ = _pair(reference_src, {}, residual, weighted)
+def test_gradients_match(golden, phase, residual, weighted):
+    arrs, meta = golden
+    case = f"{phase}/{gc.GRAD_CASES.index((residual, weighted))}"
+    ours = _ours({}, residual, weighted)
     mac, feats, ret, mask = _batch(seed=1)
-    for m in (ref, ours):
-        m.zero_grad()
-        m(mac, feats, ret, mask, phase=phase)["loss"].backward()
-    for (k, pa), (_, pb) in zip(ref.named_parameters(), ours.named_parameters()):
-        if pa.grad is None:
+    ours.zero_grad()
+    ours(mac, feats, ret, mask, phase=phase)["loss"].backward()
+    assert meta["grad_names"][case] == [k for k, _ in ours.named_parameters()]
+    ref_grads = {k: gc.tensor(arrs[f"grad/{case}/{k}"]) for k in meta["grad_names"][case]
+                 if k not in meta["grad_none"][case]}
+    g = max(float(v.abs().max()) for v in ref_grads.values())
+    for k, pb in ours.named_parameters():
+        if k not in ref_grads:
             assert pb.grad is None or torch.count_nonzero(pb.grad) == 0, k
             continue
         # fp32 reduction-order noise: tolerance relative to the tensor's scale (output_proj.bias
         # has an exactly-zero true gradient under the zero-mean normalisation)
-        g = _grad_scale(ref)
-        atol = max(2e-5 * float(pa.grad.abs().max()), 1e-5 * g)
-        torch.testing.assert_close(pb.grad, pa.grad, rtol=1e-4, atol=atol, msg=k)
+        pa = ref_grads[k]
+        atol = max(2e-5 * float(pa.abs().max()), 1e-5 * g)
+        torch.testing.assert_close(pb.grad, pa, rtol=1e-4, atol=atol, msg=lambda m, k=k: f"{k}: {m}")
 
 
-def _grad_scale(m):
-    return max(float(p.grad.abs().max()) for p in m.parameters() if p.grad is not None)
-
-
-def test_residual_loss_matches(reference_src):
-    ref, ours, _ = _pair(reference_src, {}, residual=1.0)
+def test_residual_loss_matches(golden):
+    arrs, _ = golden
+    ours = _ours({}, residual=1.0)
     mac, feats, ret, mask = _batch(seed=2)
-    mask[3] = False                      # an empty period
-    mask[4, 1:] = False                  # a period with one stock (skipped by the reference)
+    mask = gc.residual_mask(mask)
     with torch.no_grad():
         w, _ = ours.sdf_net(mac, feats, mask)
-        a = ref.compute_residual_loss(w, ret, mask)
-        b = ours.compute_residual_loss(w, ret, mask)
-    torch.testing.assert_close(b, a, rtol=1e-5, atol=1e-9)
+        torch.testing.assert_close(w, gc.tensor(arrs["residual/weights"]), rtol=2e-5, atol=1e-7)
+        # both implementations on the same weights (the reference's)
+        b = ours.compute_residual_loss(gc.tensor(arrs["residual/weights"]), ret, mask)
+    torch.testing.assert_close(b, gc.tensor(arrs["residual/loss"]), rtol=1e-5, atol=1e-9)
 
 
 @pytest.mark.parametrize("normalized", [False, True])
-def test_get_weights_and_sdf_factor(reference_src, normalized):
-    ref, ours, _ = _pair(reference_src, {})
-    ref.eval(); ours.eval()
+def test_get_weights_and_sdf_factor(golden, normalized):
+    arrs, _ = golden
+    ours = _ours({})
+    ours.eval()
     mac, feats, ret, mask = _batch(seed=4)
     with torch.no_grad():
-        wa, _ = ref.get_weights(mac, feats, mask, normalized=normalized)
         wb, _ = ours.get_weights(mac, feats, mask, normalized=normalized)
-        fa = ref.get_sdf_factor(mac, feats, ret, mask)
         fb = ours.get_sdf_factor(mac, feats, ret, mask)
-    torch.testing.assert_close(wb, wa, rtol=2e-5, atol=1e-8)
-    torch.testing.assert_close(fb, fa, rtol=2e-5, atol=1e-8)
+    torch.testing.assert_close(wb, gc.tensor(arrs[f"get_weights/{int(normalized)}"]), rtol=2e-5, atol=1e-8)
+    torch.testing.assert_close(fb, gc.tensor(arrs["sdf_factor"]), rtol=2e-5, atol=1e-8)
 
 
-def test_simple_sdf_matches(reference_src):
-    ref_model = importlib.import_module("ref_src.model")
-    torch.manual_seed(5)
-    a = ref_model.SimpleSDF(5, 10, [16, 8], dropout=0.0)
+def test_simple_sdf_matches(golden):
+    arrs, meta = golden
     torch.manual_seed(5)
     b = SimpleSDF(5, 10, [16, 8], dropout=0.0)
-    assert list(a.state_dict()) == list(b.state_dict())
+    assert meta["simple_sdf_keys"] == list(b.state_dict())
     mac, feats, ret, mask = _batch(seed=6)
-    oa, ob = a(mac, feats, ret, mask), b(mac, feats, ret, mask)
+    ob = b(mac, feats, ret, mask)
     for k in ("weights", "loss", "sharpe"):
-        torch.testing.assert_close(ob[k], oa[k], rtol=2e-5, atol=1e-8, msg=k)
+        ref = gc.tensor(arrs[f"simple_sdf/{k}"])
+        # (the weights are O(1) here: 1e-8 is a fraction of one rounding of the larger ones)
+        torch.testing.assert_close(ob[k], ref, rtol=2e-5, atol=max(1e-8, gc.ulp_atol(ref)),
+                                   msg=lambda m, k=k: f"{k}: {m}")
 
 
-def test_unknown_config_keys_are_ignored_and_quirks(reference_src):
+def test_unknown_config_keys_are_ignored_and_quirks():
     cfg = default_cli_config(5, 10)
     cfg.update(num_moments=99, rnn_hidden_dim=77, num_units_rnn=[4, 8])
     m = AssetPricingGAN(cfg)

@@ -13,8 +13,8 @@ run() { local name=$1 to=$2; shift 2
   tail -2 gpurun_out/rehearsal_$name.log | cut -c1-600 >> $OUT; }
 TR="python -m torch.distributed.run --nnodes=1 --master-addr 127.0.0.1"
 ENS="-m deeplearninginassetpricing_paperreplication_amd.parallel.ensemble --synthetic 240 60 300 3000 46 178 --epochs_unc 32 --epochs_moment 8 --epochs 64 --ignore_epoch 4"
-run bench_n2 300 $TR --nproc-per-node 2 --master-port 29511 bench.py --gpus 2 --steps 105 --warmup 12
-run bench_n4 300 $TR --nproc-per-node 4 --master-port 29512 bench.py --gpus 4 --steps 105 --warmup 12
+run bench_n2 300 $TR --nproc-per-node 2 --master-port 29511 bench.py --gpus 2 --full --steps 105 --warmup 12
+run bench_n4 300 $TR --nproc-per-node 4 --master-port 29512 bench.py --gpus 4 --full --steps 105 --warmup 12
 run ens_n1 300 $TR --nproc-per-node 1 --master-port 29513 $ENS
 run ens_n2 300 $TR --nproc-per-node 2 --master-port 29514 $ENS
 run ens_n4 300 $TR --nproc-per-node 4 --master-port 29515 $ENS
