@@ -791,6 +791,67 @@ class Engine {
     if (graphs_dirty_) { rebuild_jobs(); graphs_dirty_ = false; }
     fwd_only(s, train_mode, do_mom, wait);
   }
+  // Variable importance of split s (k_sens.hip): the gradient of the raw SDF weight with respect to
+  // the layer-0 input row -- the F characteristics, then the Dm per-period columns (LSTM state, or
+  // raw macro) -- reduced over the split's rows. `scale`: device fp32 [G][T] factor of model g's
+  // gradient in period t (0: ones), read on the engine stream. Returns fp64 arrays
+  //   abs [G][C] = sum_rows |dx_g|, sum [G][C] = sum_rows dx_g, ens [C] = sum_rows |sum_g dx_g|
+  // and rows (= R). refresh: run the evaluation forward of the split first (its prologue produces
+  // the per-period inputs); false when the caller has just done so (forward_split(s, false, ...)).
+  bool sens_ok() const { return sens_supported(md_.md, md_.KS1); }
+  py::dict input_sensitivity(int s, uintptr_t scale, bool refresh = true) {
+    if (s < 0 || s > 2) throw std::invalid_argument("split must be 0, 1 or 2");
+    if (graphs_dirty_) { rebuild_jobs(); graphs_dirty_ = false; }
+    const SplitDev& D = splits_[s];
+    if (!D.set) throw std::runtime_error("split not set");
+    if (!sens_supported(md_.md, md_.KS1))
+      throw std::invalid_argument("input_sensitivity: not available for this shape (wide layer-0 path, or the "
+                                  "fragments exceed the LDS budget)");
+    const int C = md_.F + md_.Dm, nrows = 2 * G_ + 1;
+    std::vector<double> host((size_t)nrows * C, 0.0);
+    if (D.R > 0) {                            // (an empty split launches nothing and reads nothing)
+      if (refresh) fwd_only(s, false, false, false);
+      // buffers of this call (an analysis pass, not a step of an epoch): job tables, [G][T]
+      // scales, chunk partials, fp64 result -- released on return, after the final sync
+      DevBuf<char> tj, tsj;
+      DevBuf<float> scl, part;
+      DevBuf<double> res;
+      const size_t ns = (size_t)G_ * D.T;
+      scl.alloc(ns, false);
+      if (scale) {
+        HIP_OK(hipMemcpyAsync(scl.p, reinterpret_cast<const void*>(scale), ns * sizeof(float),
+                              hipMemcpyDeviceToDevice, st_));
+      } else {
+        sync();
+        const std::vector<float> ones(ns, 1.f);
+        HIP_LEGACY(hipMemcpy(scl.p, ones.data(), ns * sizeof(float), hipMemcpyHostToDevice));
+      }
+      std::vector<MlpJob> mj;
+      std::vector<SensJob> sj;
+      for (int g = 0; g < G_; ++g) {
+        mj.push_back(mlp_job(g, s, false, true, false));
+        sj.push_back(SensJob{models_[g].params.p, scl.p + (size_t)g * D.T});
+      }
+      upload(tj, mj);
+      upload(tsj, sj);
+      part.alloc(sens_part_floats(D.R, G_, md_.KS1), false);
+      res.alloc(host.size(), false);
+      launch_input_sens(as<MlpJob>(tj), as<SensJob>(tsj), G_, D.R, md_.md, md_.KS1, md_.s[0],
+                        part.p, res.p, st_);
+      sync();
+      HIP_LEGACY(hipMemcpy(host.data(), res.p, host.size() * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    py::array_t<double> a({G_, C}), b({G_, C}), e({C});
+    for (int g = 0; g < G_; ++g)
+      for (int c = 0; c < C; ++c) {
+        a.mutable_at(g, c) = host[(size_t)(2 * g) * C + c];
+        b.mutable_at(g, c) = host[(size_t)(2 * g + 1) * C + c];
+      }
+    for (int c = 0; c < C; ++c) e.mutable_at(c) = host[(size_t)(2 * G_) * C + c];
+    py::dict d;
+    d["abs"] = a; d["sum"] = b; d["ens"] = e; d["rows"] = D.R;
+    return d;
+  }
   void train_step(int phase, float lr) {
     if (graphs_dirty_) { rebuild_jobs(); graphs_dirty_ = false; }
     if (phase == 2) h_valid_ = false;
@@ -2559,6 +2620,9 @@ PYBIND11_MODULE(_dlap_hip, m) {
       .def("grads_ptr", &Engine::grads_ptr)
       .def("forward_split", &Engine::forward_split, py::arg("s"), py::arg("train_mode"), py::arg("do_mom"),
            py::arg("wait") = true)
+      .def("input_sensitivity", &Engine::input_sensitivity, py::arg("s"), py::arg("scale") = 0,
+           py::arg("refresh") = true)
+      .def("sens_supported", [](Engine& e) { return e.sens_ok(); })
       .def("train_step", &Engine::train_step)
       .def("backward_only", &Engine::backward_only, py::arg("phase"), py::arg("wait") = true)
       .def("set_stream", &Engine::set_stream, py::arg("stream"), py::arg("external") = true)

@@ -136,3 +136,18 @@ void launch_tbwd_sdf(const MlpJob* jobs, int njobs, int gx, const MlpDims& D, in
 std::vector<long long> tbwd_timestamps();
 
 std::vector<long long> mlp_timestamps();
+
+// variable importance (k_sens.hip): d w_raw / d (layer-0 input row), reduced over the rows of a
+// split. jobs: the split's evaluation tower jobs of the G models; sj: their fp32 parameter vectors
+// and per-period scales; part: sens_part_floats() floats of chunk partials; out: fp64
+// [2 G + 1][F + Dm] -- rows 2g / 2g + 1 = sum |dx_g| / sum dx_g, row 2G = sum |sum_g dx_g|.
+struct SensJob {
+  const float* params;    // the model's flat fp32 parameter vector (W0^T is built from it)
+  const float* scale;     // [T] scale of the model's output gradient per period
+};
+struct PackLayer;
+bool sens_supported(const MlpDims& D, int KS1);
+int sens_chunks(int R);                       // a function of R only (the summation order)
+size_t sens_part_floats(int R, int G, int KS1);
+void launch_input_sens(const MlpJob* jobs, const SensJob* sj, int G, int R, const MlpDims& D, int KS1,
+                       const PackLayer& L0, float* part, double* out, hipStream_t st);

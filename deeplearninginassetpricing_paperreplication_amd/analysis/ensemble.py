@@ -86,9 +86,13 @@ def weights_batched_gpu(models: Sequence, batches: Dict[str, Dict]) -> Dict[str,
 
 
 def evaluate_ensemble(checkpoint_dirs: Sequence[str], data_dir: str, device: str = "cpu",
-                      verbose: bool = True, paper: bool = False) -> Dict:
+                      verbose: bool = True, paper: bool = False, importance: bool = False,
+                      importance_split: str = "test", importance_out: str = None) -> Dict:
     """Reference output and return value; ``paper=True`` (CLI ``--paper_metrics``) adds the
-    paper's EV / XS-R² / turnover / max 1-month loss of the ensemble's SDF factor per split."""
+    paper's EV / XS-R² / turnover / max 1-month loss of the ensemble's SDF factor per split;
+    ``importance=True`` (CLI ``--variable_importance``) adds the sensitivity ranking of the
+    ensemble weight on ``importance_split`` (``analysis.importance``) under the key
+    ``variable_importance`` and writes it to ``importance_out`` (JSON) when given."""
     say = print if verbose else (lambda *a, **k: None)
     bar = "=" * 70
     say(bar); say(f"ENSEMBLE EVALUATION ({len(checkpoint_dirs)} models, averaged weights)"); say(bar); say()
@@ -143,6 +147,22 @@ def evaluate_ensemble(checkpoint_dirs: Sequence[str], data_dir: str, device: str
             say(f"  {s.capitalize():5s}  SR {pm['sharpe']:7.4f}  EV {pm['ev']:7.4f}  XS-R2 {pm['xs_r2']:7.4f}  "
                 f"turnover {pm['turnover']:6.3f}  max 1m loss {pm['max_1m_loss_std']:5.2f} sd")
         say()
+    if importance:
+        from .importance import format_importance, to_json, variable_importance
+        if importance_split not in SPLITS:
+            raise ValueError(f"importance_split must be one of {SPLITS}")
+        ds = datasets[SPLITS.index(importance_split)]
+        imp = variable_importance(models, batches[importance_split], device=device,
+                                  names=getattr(ds, "variable_names", None))
+        out["variable_importance"] = imp
+        say(bar); say(f"VARIABLE IMPORTANCE ({importance_split} split, ensemble weight)"); say(bar); say()
+        for line in format_importance(imp):
+            say(line)
+        say()
+        if importance_out:
+            with open(importance_out, "w") as fh:
+                json.dump(to_json(imp), fh, indent=1)
+            say(f"  Saved: {importance_out}"); say()
     return out
 
 
@@ -152,8 +172,14 @@ def main(argv=None):
     p.add_argument("--checkpoint_dirs", type=str, nargs="+", required=True)
     p.add_argument("--device", type=str, default="cpu", help="cpu | cuda (batched native engine)")
     p.add_argument("--paper_metrics", action="store_true", help="also print EV / XS-R2 / turnover / max loss")
+    p.add_argument("--variable_importance", action="store_true",
+                   help="also print the sensitivity ranking of the ensemble weight")
+    p.add_argument("--importance_split", type=str, default="test", choices=SPLITS)
+    p.add_argument("--importance_out", type=str, default=None, help="write the ranking to FILE.json")
     a = p.parse_args(argv)
-    return evaluate_ensemble(a.checkpoint_dirs, a.data_dir, a.device, paper=a.paper_metrics)
+    return evaluate_ensemble(a.checkpoint_dirs, a.data_dir, a.device, paper=a.paper_metrics,
+                             importance=a.variable_importance, importance_split=a.importance_split,
+                             importance_out=a.importance_out)
 
 
 if __name__ == "__main__":

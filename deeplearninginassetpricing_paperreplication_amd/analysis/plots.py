@@ -200,7 +200,29 @@ def plot_summary_statistics(checkpoint_dirs, data_dir, save_path=None, panel: _P
     return fig, ax
 
 
-def generate_all_plots(checkpoint_dirs, data_dir, output_dir="./plots", device: str = "cpu"):
+def plot_variable_importance(checkpoint_dirs, data_dir, save_path=None, device: str = "cpu",
+                             split: str = "test", top: int = 20, importance: Dict = None):
+    """Horizontal bars of the ``top`` characteristics by sensitivity of the ensemble weight."""
+    if importance is None:
+        from .importance import variable_importance
+        ds = load_splits(data_dir)[SPLITS.index(split)]
+        models = [load_model(d, "cpu")[0] for d in checkpoint_dirs]
+        importance = variable_importance(models, ds.get_full_batch(), device=device,
+                                         names=getattr(ds, "variable_names", None))
+    ch = np.asarray(importance["characteristics"])
+    order = np.argsort(-ch)[:top][::-1]
+    fig, ax = plt.subplots(figsize=(10, 8))
+    ax.barh(np.arange(len(order)), ch[order], color="steelblue", alpha=0.8, edgecolor="black")
+    ax.set_yticks(np.arange(len(order)))
+    ax.set_yticklabels([importance["names"][j] for j in order])
+    ax.set(xlabel="Sensitivity (share of mean |dw/dx|)", title=f"Variable Importance (Top {len(order)}, {split})")
+    ax.grid(True, alpha=0.3, axis="x")
+    _save(fig, save_path)
+    return fig, ax
+
+
+def generate_all_plots(checkpoint_dirs, data_dir, output_dir="./plots", device: str = "cpu",
+                       variable_importance: bool = False):
     os.makedirs(output_dir, exist_ok=True)
     print("Generating plots...")
     print("=" * 50)
@@ -216,6 +238,9 @@ def generate_all_plots(checkpoint_dirs, data_dir, output_dir="./plots", device: 
         ("Summary Statistics", "summary_statistics.png",
          lambda p: plot_summary_statistics(checkpoint_dirs, data_dir, p, panel=panel)),
     ]
+    if variable_importance:
+        jobs.append(("Variable Importance", "variable_importance.png",
+                     lambda p: plot_variable_importance(checkpoint_dirs, data_dir, p, device=device)))
     for i, (title, fname, fn) in enumerate(jobs, 1):
         print(f"\n{i}. {title}...")
         fn(os.path.join(output_dir, fname))
@@ -231,8 +256,13 @@ def main(argv=None):
                    help="Paths to checkpoint directories")
     p.add_argument("--output_dir", type=str, default="./plots", help="Output directory for plots")
     p.add_argument("--device", type=str, default="cpu")
+    p.add_argument("--variable_importance", action="store_true",
+                   help="also write variable_importance.png (top 20 characteristics)")
     a = p.parse_args(argv)
-    generate_all_plots(a.checkpoint_dirs, a.data_dir, a.output_dir, a.device)
+    if a.variable_importance:
+        generate_all_plots(a.checkpoint_dirs, a.data_dir, a.output_dir, a.device, variable_importance=True)
+    else:
+        generate_all_plots(a.checkpoint_dirs, a.data_dir, a.output_dir, a.device)
 
 
 if __name__ == "__main__":
