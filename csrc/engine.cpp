@@ -33,9 +33,11 @@
 #include <string>
 #include <vector>
 
+#include <chrono>
+
+#include "engine_plan.h"
 #include "layout.h"
 #include "loss.h"
-#include <chrono>
 #include "mlp.h"
 #include "panel.h"
 #include "rnn.h"
@@ -116,6 +118,10 @@ template <typename T>
 struct DevBuf {
   T* p = nullptr;
   size_t n = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;            // owns device memory
+  DevBuf& operator=(const DevBuf&) = delete;
+  DevBuf(DevBuf&& o) noexcept : p(o.p), n(o.n) { o.p = nullptr; o.n = 0; }
   void alloc(size_t count, bool zero = true) {
     free();
     n = count;
@@ -172,19 +178,6 @@ struct ModelState {
 
 }  // namespace
 
-// Per-model workgroups of a tower launch over G batched models (grid.y = model): the single-
-// model grid tuned at 600x3000 (`one`) divided by G, at least `lo`. The whole launch then keeps
-// roughly the single-model workgroup count instead of G times it: fewer weight stagings per
-// row and, in the backward, G-fold fewer gradient slabs for k_finalize to reduce. Measured
-// (profiles/r3_knobs_grids_batched.log): 9 models 1.045 -> 0.823 ms per epoch, 2 models
-// 0.337 -> 0.271 ms.
-static int grid_per_model(int one, int lo, int G) { return std::max(lo, one / std::max(1, G)); }
-
-static int env_int(const char* name, int dflt) {
-  const char* v = std::getenv(name);
-  return v && *v ? std::atoi(v) : dflt;
-}
-
 static void install_crash_handler();
 // DLAP_TRACE_HOST=1: one stderr line per host-side engine step (crash localisation on boxes
 // where a native backtrace is not available)
@@ -196,7 +189,7 @@ class Engine {
   Engine(int F, int M, int nrnn, int H, bool raw_macro_sdf, std::vector<int> hidden,
          std::vector<int> mom_hidden, int K, float dropout, bool normalize_w, bool weighted,
          float residual, int G, int max_epochs, bool fp32)
-      : G_(G), max_epochs_(max_epochs) {
+      : G_(G), max_epochs_(max_epochs), k_(read_knobs(G, fp32)) {
     g_live_engines.fetch_add(1);
     HIP_OK(hipStreamCreateWithFlags(&st_, hipStreamNonBlocking));
     {
@@ -217,46 +210,9 @@ class Engine {
       HIP_OK(hipExtStreamCreateWithCUMask(&st2_, (uint32_t)mask.size(), mask.data()));
     }
     own_st_ = st_;
-    HIP_OK(hipEventCreateWithFlags(&ev_fork_, hipEventDisableTiming));
-    HIP_OK(hipEventCreateWithFlags(&ev_join_, hipEventDisableTiming));
-    HIP_OK(hipEventCreateWithFlags(&ev_gram_, hipEventDisableTiming));
-    HIP_OK(hipEventCreateWithFlags(&ev_trgram_, hipEventDisableTiming));
-    HIP_OK(hipEventCreateWithFlags(&ev_mid_, hipEventDisableTiming));
-    HIP_OK(hipEventCreateWithFlags(&ev_a_, hipEventDisableTiming));
-    HIP_OK(hipEventCreateWithFlags(&ev_in_, hipEventDisableTiming));
-    HIP_OK(hipEventCreateWithFlags(&ev_out_, hipEventDisableTiming));
-    // evaluation tower grid cap: with the split epoch graphs the evaluation branch has slack and
-    // its towers start beside the training chain's loss passes; a narrower grid takes fewer CUs
-    // from them -- 224-256 measured best (phase 3 0.1554 vs 0.164 ms at 384, profiles/
-    // r5_knobs_eval_gx.log; 384 was best on the round-3 tree). Per job: with G batched models the
-    // launch has 2G evaluation jobs, so the per-job grid shrinks with G (see grid_per_model)
-    eval_gx_ = env_int("DLAP_EVAL_GX", grid_per_model(256, 64, G));
-    zx_eval_ = env_int("DLAP_ZX_EVAL", 1) != 0;
-    zx_train_ = env_int("DLAP_ZX_TRAIN", 1) != 0;
-    zx_gx_ = std::max(1, env_int("DLAP_ZX_GX", 256));
-    h_cache_ = env_int("DLAP_H_CACHE", 1) != 0;
-    gram_on_ = env_int("DLAP_GRAM", 1) != 0;
-    rnn_overlap_ = env_int("DLAP_RNN_OVERLAP", 1) != 0;
-    rnn_overlap_eval_ = env_int("DLAP_RNN_OVERLAP_EVAL", 0) != 0;
-    prog_mode_ = env_int("DLAP_PROG_MODE", 1);
-    prog_limit_ = (unsigned)env_int("DLAP_PROG_SPIN_LIMIT", 1 << 22);
-    fused_p2_ = env_int("DLAP_FUSED_PHASE2", 0) != 0;
-    eval_in_fwd_ = env_int("DLAP_EVAL_IN_FWD", 1) != 0;
-    eval_sep_ = env_int("DLAP_EVAL_SEP", 0) != 0;
-    fused_tail_ = env_int("DLAP_FUSED_TAIL", 1) != 0;
-    self_proj_ = env_int("DLAP_SELF_PROJ", 1) != 0;
-    tail_adam_ = env_int("DLAP_TAIL_ADAM", 1) != 0;
-    tail_adam_pipe_ = env_int("DLAP_TAIL_ADAM", 1) == 2;
-    split_graphs_ = env_int("DLAP_SPLIT_GRAPHS", 1) != 0;
-    mom_tail_ = env_int("DLAP_MOM_TAIL", 1) != 0;
-    train_gram_side_ = env_int("DLAP_TRAIN_GRAM_SIDE", 0) != 0;
-    p2_lstm_cache_ = env_int("DLAP_P2_LSTM_CACHE", 1) != 0;
-    unroll_ = std::max(1, env_int("DLAP_UNROLL", 8));
+    for (hipEvent_t& e : ev_) HIP_OK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     build_desc(F, M, nrnn, H, raw_macro_sdf, hidden, mom_hidden, K, dropout, normalize_w, weighted,
                residual, fp32);
-    // fp32 wide path: layer 0 through k_proj0 + the ZIN towers (the fused-layer-0 k_mlp_fwd_zx
-    // is bf16 only)
-    if (fp32) zx_eval_ = zx_train_ = false;
     prog_.alloc((size_t)G * 3 * 16);      // per (model, split): [0] published periods, [1] spin timeouts
     esync_.alloc(64);                      // split epoch graphs: [0] evaluation recurrences done, [32] consumed
     d_desc_.alloc(sizeof(ModelDesc));
@@ -285,7 +241,7 @@ class Engine {
   // fixed-width lists per parameter (PACK_FAN slots). Without them (DLAP_FUSED_PACK=0, indices
   // past fp32's exact integers, or a parameter with more copies) k_pack runs after k_adam.
   void build_pack_inverse() {
-    if (env_int("DLAP_FUSED_PACK", 1) == 0 || md_.P >= (1 << 24)) return;
+    if (!k_.fused_pack || md_.P >= (1 << 24)) return;
     const int total = pack_total(md_);
     std::vector<int> h(total);
     pack_index_host(md_, h.data());
@@ -320,12 +276,7 @@ class Engine {
     if (st_) (void)hipStreamSynchronize(st_);
     if (own_st_ && own_st_ != st_) (void)hipStreamSynchronize(own_st_);
     for (auto& kv : graphs_) retire_graph_exec(kv.second, st_);
-    if (ev_fork_) (void)hipEventDestroy(ev_fork_);
-    if (ev_join_) (void)hipEventDestroy(ev_join_);
-    if (ev_gram_) (void)hipEventDestroy(ev_gram_);
-    if (ev_mid_) (void)hipEventDestroy(ev_mid_);
-    if (ev_a_) (void)hipEventDestroy(ev_a_);
-    for (hipEvent_t e : {ev_in_, ev_out_}) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : ev_) if (e) (void)hipEventDestroy(e);
     if (st2_) (void)hipStreamDestroy(st2_);
     if (own_st_) (void)hipStreamDestroy(own_st_);
     (void)hipGetLastError();      // (ignored statuses above must not fail the next launch check)
@@ -634,7 +585,7 @@ class Engine {
   // Reset the per-phase trackers (reference: fresh best values per phase).
   // Stream-ordered (k_begin_phase after the queued epochs): no host synchronisation.
   void begin_phase(int phase) {
-    if (graphs_dirty_) { rebuild_jobs(); graphs_dirty_ = false; }
+    ensure_jobs();
     const int p = (phase >= 1 && phase <= 3) ? phase : 1;   // any phase's table names the trackers
     launch_begin_phase(as<EpochJob>(j_epoch_[p]), G_, st_);
   }
@@ -670,52 +621,43 @@ class Engine {
     HTRACE("run_epochs phase=%d n=%d graph=%d dirty=%d", phase, n, (int)use_graph, (int)graphs_dirty_);
     if (!splits_[0].set) throw std::runtime_error("train split not set");
     if (ext_stream_) throw std::runtime_error("run_epochs needs the engine's own streams (set_stream(0, False))");
-    if (graphs_dirty_) { rebuild_jobs(); graphs_dirty_ = false; }
+    check_phase(phase);
+    ensure_jobs();
     if (n <= 0) return;
-    const bool pipe = phase != 2 && n_eval_jobs_ > 0 && pipeline_;
+    const RunMode mode = run_mode(phase);
     // the moment net trains in phase 2: the cached moments go stale. Else refresh them (and the
     // Gram matrices); with the pipelined graphs the evaluation splits' Gram builds overlap the
     // head epoch (which trains only) on the evaluation stream
-    cur_phase_ = phase;
     if (phase == 2) h_valid_ = false;
-    else ensure_moments(true, pipe && use_graph);
+    else ensure_moments(phase, mode.pipe && use_graph);
     // phase 2: the frozen SDF's LSTM state (no inter-layer dropout) is the same every epoch --
     // computed once here, the epochs project only the moment network's bias table
-    if (phase == 2 && p2_lstm_cached()) {
+    const bool lstm_once = plan_[phase].p2_lstm_cached;
+    if (lstm_once) {
       HTRACE("launch_prologue(phase-2 LSTM, once)");
       launch_prologue(as<RnnJob>(j_rnn_train_), G_, splits_[0].T, dd(), md_, st_, false, true);
-      lstm_once_ = true;
     }
-    struct OnceScope {
-      bool& f;
-      ~OnceScope() { f = false; }
-    } once_scope{lstm_once_};
-    struct GramScope {                    // epoch graphs run the loss in Gram mode
-      bool& f;
-      explicit GramScope(bool& x) : f(x) { f = true; }
-      ~GramScope() { f = false; }
-    } gram_scope(gram_run_);
     if (!use_graph || xs_on_) {          // (sharded: the hooks' collectives are enqueued per epoch)
-      for (int e = 0; e < n; ++e) enqueue_epoch(phase, lr, ignore_epoch, sel);
+      for (int e = 0; e < n; ++e) enqueue_epoch(phase, lr, ignore_epoch, sel, lstm_once);
       return;
     }
     // One executor per epoch graph. (Measured and dropped in round 4: alternating several
     // executors of the same graph -- every hipGraphLaunch of these multi-branch graphs blocks the
     // host ~one epoch, and the wait is not per executor, profiles/r4_hostgaps_short.txt -- and
     // unrolling several pipelined epochs into one graph: both 2-5% slower.)
-    if (!pipe) {
-      hipGraphExec_t g = graph_for(graph_key(phase, lr, ignore_epoch, sel, 200 + 10 * (int)lstm_once_ + (int)mom_tail_on(phase)),
-                                   [&] { enqueue_epoch(phase, lr, ignore_epoch, sel); });
+    if (!mode.pipe) {
+      hipGraphExec_t g = graph_for(graph_key(phase, lr, ignore_epoch, sel, 200 + 10 * (int)lstm_once + (int)plan_[phase].mom_tail),
+                                   [&] { enqueue_epoch(phase, lr, ignore_epoch, sel, lstm_once); });
       for (int e = 0; e < n; ++e) HIP_OK(hipGraphLaunch(g, st_));
       return;
     }
-    if (split_graphs(phase)) {
-      // the body epochs in graphs of `unroll_` epochs each (the rest one by one): a graph boundary
+    if (mode.split) {
+      // the body epochs in graphs of `unroll` epochs each (the rest one by one): a graph boundary
       // costs ~5-9 us (the last node's system-scope release, the first one's acquire); inside a
       // graph consecutive kernels of one queue follow each other directly
       // (both graphs are captured on the first call, whatever n: the bench's warmup captures
       // what its timed region launches)
-      const int nbody = n - 1, ku = unroll_;
+      const int nbody = n - 1, ku = k_.unroll;
       hipGraphExec_t chain = graph_for(graph_key(phase, lr, ignore_epoch, sel, 21),
                                        [&] { enqueue_chain_split(phase, lr); });
       hipGraphExec_t evalg = graph_for(graph_key(phase, lr, ignore_epoch, sel, 22),
@@ -732,8 +674,8 @@ class Engine {
       launch_head(phase, lr, ignore_epoch, sel);
       join_eval_gram();
       // the evaluation graphs follow the head on st2_ (its masks / step counters, its weights)
-      HIP_OK(hipEventRecord(ev_fork_, st_));
-      HIP_OK(hipStreamWaitEvent(st2_, ev_fork_, 0));
+      HIP_OK(hipEventRecord(ev_[EV_FORK], st_));
+      HIP_OK(hipStreamWaitEvent(st2_, ev_[EV_FORK], 0));
       const auto t_l = std::chrono::steady_clock::now();
       int e = 0;
       for (; e + ku <= nbody; e += ku) {
@@ -748,8 +690,8 @@ class Engine {
       host_launch_n_ += n - 1;
       // (the last evaluation graph finished before the last chain's update: one event for the
       // stream order the host and later launches rely on)
-      HIP_OK(hipEventRecord(ev_join_, st2_));
-      HIP_OK(hipStreamWaitEvent(st_, ev_join_, 0));
+      HIP_OK(hipEventRecord(ev_[EV_JOIN], st2_));
+      HIP_OK(hipStreamWaitEvent(st_, ev_[EV_JOIN], 0));
       HIP_OK(hipGraphLaunch(tail, st_));
       return;
     }
@@ -774,21 +716,17 @@ class Engine {
   // graphs, no Adam in the tail (waits inside one launch on lower-numbered, already dispatched
   // blocks stay). The graphs are rebuilt.
   void set_safe_mode(bool on) {
-    safe_mode_ = on;
-    rnn_overlap_ = on ? false : env_int("DLAP_RNN_OVERLAP", 1) != 0;
-    split_graphs_ = on ? false : env_int("DLAP_SPLIT_GRAPHS", 1) != 0;
-    tail_adam_ = on ? false : env_int("DLAP_TAIL_ADAM", 1) != 0;
+    safe_mode_ = on;                          // (plan_phases overlays it on the latched switches)
     // the waits left (inside one launch, on blocks dispatched ahead) get the default patience
-    if (on) prog_limit_ = std::max(prog_limit_, 1u << 22);
+    if (on) k_.spin_limit = std::max(k_.spin_limit, 1u << 22);
     graphs_dirty_ = true;
   }
-  bool safe_mode_ = false;
   // job tables (and the fused launches' co-residency capacities) current
   void ensure_jobs() { if (graphs_dirty_) { rebuild_jobs(); graphs_dirty_ = false; } }
 
   // Pieces used by the module-level API / tests (no bookkeeping).
   void forward_split(int s, bool train_mode, bool do_mom, bool wait = true) {
-    if (graphs_dirty_) { rebuild_jobs(); graphs_dirty_ = false; }
+    ensure_jobs();
     fwd_only(s, train_mode, do_mom, wait);
   }
   // Variable importance of split s (k_sens.hip): the gradient of the raw SDF weight with respect to
@@ -801,7 +739,7 @@ class Engine {
   bool sens_ok() const { return sens_supported(md_.md, md_.KS1); }
   py::dict input_sensitivity(int s, uintptr_t scale, bool refresh = true) {
     if (s < 0 || s > 2) throw std::invalid_argument("split must be 0, 1 or 2");
-    if (graphs_dirty_) { rebuild_jobs(); graphs_dirty_ = false; }
+    ensure_jobs();
     const SplitDev& D = splits_[s];
     if (!D.set) throw std::runtime_error("split not set");
     if (!sens_supported(md_.md, md_.KS1))
@@ -853,16 +791,18 @@ class Engine {
     return d;
   }
   void train_step(int phase, float lr) {
-    if (graphs_dirty_) { rebuild_jobs(); graphs_dirty_ = false; }
+    check_phase(phase);
+    ensure_jobs();
     if (phase == 2) h_valid_ = false;
     else ensure_moments();
     enqueue_train(phase, lr);
   }
   void backward_only(int phase, bool wait = true) {   // losses + gradients, no optimiser step
     HTRACE("backward_only phase=%d tid=%ld", phase, (long)syscall(SYS_gettid));
-    if (graphs_dirty_) { rebuild_jobs(); graphs_dirty_ = false; }
+    check_phase(phase);
+    ensure_jobs();
     if (phase != 2) ensure_moments();
-    enqueue_train_grads(phase);
+    enqueue_train_grads(TrainPass(phase));
     if (wait) sync();
   }
 
@@ -877,8 +817,8 @@ class Engine {
   // dh (phase 2, module API): an external dL/dh [T*N][K] (dense, the moments of the train split)
   // instead of dE / sdf -- a caller's loss of the moments.
   void xs_backward(int phase, uintptr_t dw, uintptr_t dE, uintptr_t sdf, uintptr_t dh = 0) {
-    if (graphs_dirty_) { rebuild_jobs(); graphs_dirty_ = false; }
-    if (phase < 1 || phase > 3) throw std::invalid_argument("phase must be 1, 2 or 3");
+    check_phase(phase);
+    ensure_jobs();
     if (dh) {
       if (phase != 2) throw std::invalid_argument("an external dL/dh needs phase 2 (the moment tower)");
       const SplitDev& D = splits_[0];
@@ -899,22 +839,9 @@ class Engine {
     }
     if (phase != 2) ensure_moments();
     const SplitDev& D = splits_[0];
-    enqueue_dropmask(phase, 0, st_);
-    const bool fused = fused_fwd(phase);
-    if (fused) launch_proj(as<RnnJob>(j_rnn_train_), G_, D.T, dd(), md_, st_, train_mom(phase));
-    else launch_prologue(as<RnnJob>(j_rnn_train_), G_, D.T, dd(), md_, st_, train_mom(phase));
-    const bool zx_train = md_.md.wide && zx_train_;
-    if (md_.md.wide && !zx_train)
-      launch_proj0(as<WideJob>(j_wide_train_[phase]), G_, gx_proj_[0], md_.md, md_.WMB, st_);
-    if (zx_train)
-      launch_mlp_fwd_zx(as<MlpJob>(j_mlp_train_[phase]), G_, std::max(1, zx_gx_ / G_), md_.md, md_.WMB, st_, true);
-    else if (fused)
-      launch_mlp_fwd_rnn(as<MlpJob>(j_mlp_train_[phase]), as<RnnJob>(j_rnn_train_), dd(), G_,
-                         fused_train_gx(phase), md_.md, md_.KS1, md_.WMB, md_.H, md_.nrnn, D.T, st_,
-                         !train_mom(phase));
-    else
-      launch_mlp_fwd(as<MlpJob>(j_mlp_train_[phase]), G_, phase == 2 ? gx_fwd_[0] : gx_fwd13_, md_.md, md_.KS1,
-                     md_.WMB, st_, !train_mom(phase));
+    TrainPass tp(phase);
+    tp.own_proj = false;                      // (k_proj projects the recurrence's inputs)
+    enqueue_train_fwd(tp);
     for (int g = 0; g < G_; ++g) {
       ModelSplitWS& W = ws(g, 0);
       if (phase == 2 && dh) {
@@ -938,7 +865,7 @@ class Engine {
       launch_sdf_bwd(as<MlpJob>(j_mlp_bwd_[phase]));
     if (md_.md.wide)
       launch_wgrad0(as<WideJob>(j_wide_bwd_[phase]), G_, dd(), md_.md, phase == 2, md_.WMB, nsplit_, st_);
-    enqueue_train_tail(phase);
+    enqueue_train_tail(tp);
   }
   long split_rows(int s) const { return splits_[s].R; }
 
@@ -962,12 +889,12 @@ class Engine {
   // engine calls with these, so the engine never runs on the caller's (possibly legacy) stream
   // and no host synchronisation is needed.
   void join_from(uintptr_t ext) {
-    HIP_OK(hipEventRecord(ev_in_, reinterpret_cast<hipStream_t>(ext)));
-    HIP_OK(hipStreamWaitEvent(st_, ev_in_, 0));
+    HIP_OK(hipEventRecord(ev_[EV_IN], reinterpret_cast<hipStream_t>(ext)));
+    HIP_OK(hipStreamWaitEvent(st_, ev_[EV_IN], 0));
   }
   void join_to(uintptr_t ext) {
-    HIP_OK(hipEventRecord(ev_out_, st_));
-    HIP_OK(hipStreamWaitEvent(reinterpret_cast<hipStream_t>(ext), ev_out_, 0));
+    HIP_OK(hipEventRecord(ev_[EV_OUT], st_));
+    HIP_OK(hipStreamWaitEvent(reinterpret_cast<hipStream_t>(ext), ev_[EV_OUT], 0));
   }
   // parameters from device memory (a flat fp32 vector in state_dict order), re-packed in order
   void set_params_dev(int g, uintptr_t src) {
@@ -1052,9 +979,8 @@ class Engine {
   }
   // (re)build the Gram matrices from the current moments now (tests; run_epochs does it itself)
   void refresh_gram() {
-    if (graphs_dirty_) { rebuild_jobs(); graphs_dirty_ = false; }
-    cur_phase_ = 0;                          // every split's matrices
-    ensure_moments(true);
+    ensure_jobs();
+    ensure_moments(0);                       // every split's matrices
   }
   bool gram_enabled(int phase) const { return phase == 0 ? gram_eval() : gram_train(phase); }
   // Cost model of the loss mode of one phase: the Gram form saves the dense
@@ -1069,7 +995,7 @@ class Engine {
   void plan_phase(int phase, int epochs) {
     if (phase < 1 || phase > 3) return;
     plan_tr_[phase] = plan_ev_[phase] = true;
-    if (phase == 2 || epochs <= 0 || xs_on_ || env_int("DLAP_GRAM_PLAN", 1) == 0) return;
+    if (phase == 2 || epochs <= 0 || xs_on_ || k_.gram_plan == 0) return;
     // costs in us. The training chain's dense loss (period pass, asset pass, metrics, period
     // backward) over the Gram one: a T N + b T N K (the conditional loss's moment sums), minus
     // the quadratic forms' cq T^2 -- calibrated on the split-graph pipeline at 600x3000x46:
@@ -1095,9 +1021,8 @@ class Engine {
     }
     plan_ev_[phase] = epochs * save > build;
     // (A/B of the plan: DLAP_GRAM_PLAN=2 dense evaluation splits, 3 dense train split)
-    const int force = env_int("DLAP_GRAM_PLAN", 1);
-    if (force == 2) plan_ev_[phase] = false;
-    if (force == 3) plan_tr_[phase] = false;
+    if (k_.gram_plan == 2) plan_ev_[phase] = false;
+    if (k_.gram_plan == 3) plan_tr_[phase] = false;
   }
   py::tuple gram_plan(int phase) const {
     const int p = (phase >= 1 && phase <= 3) ? phase : 1;
@@ -1168,6 +1093,8 @@ class Engine {
 
  private:
   int G_, max_epochs_;
+  Knobs k_;                                  // the DLAP_* switches, latched at construction
+  bool safe_mode_ = false;                   // set_safe_mode: overlay on k_ (no in-kernel cross-launch waits)
   hipStream_t st_ = nullptr;
   hipStream_t own_st_ = nullptr;             // the engine's stream (st_ may be an external one)
   bool ext_stream_ = false;
@@ -1176,36 +1103,29 @@ class Engine {
   struct FwdTables { DevBuf<char> r, m, l, w; bool built = false; };
   std::map<int, FwdTables> fwd_tables_;      // module-API forward job tables (per split / mode)
   hipStream_t st2_ = nullptr;                // evaluation branch of the pipelined epoch graph
-  hipEvent_t ev_fork_ = nullptr, ev_join_ = nullptr, ev_mid_ = nullptr, ev_a_ = nullptr;
-  hipEvent_t ev_in_ = nullptr, ev_out_ = nullptr;   // join_from / join_to
-  hipEvent_t ev_gram_ = nullptr;                     // deferred evaluation-split Gram builds done
-  bool eval_gram_pending_ = false;
-  int eval_gx_ = 0;                          // cap on the evaluation tower grid (DLAP_EVAL_GX)
-  bool zx_eval_ = true;                      // wide path: fused layer-0 evaluation towers (DLAP_ZX_EVAL)
-  bool zx_train_ = true;                     // ... and training forward (DLAP_ZX_TRAIN)
-  int zx_gx_ = 256;                          // their workgroups over all evaluation jobs (DLAP_ZX_GX)
-                                             // (2: with the evaluation LSTM prologue right behind the training one)
+  // fork / join of the two streams, after the loss pass, after the tower forward, join_from /
+  // join_to, deferred evaluation-split / train-split Gram builds done
+  enum { EV_FORK, EV_JOIN, EV_MID, EV_FWD, EV_IN, EV_OUT, EV_GRAM, EV_TRGRAM, EV_COUNT };
+  hipEvent_t ev_[EV_COUNT] = {};
+  bool eval_gram_pending_ = false, train_gram_pending_ = false;
   // Moment cache: the moment net only changes in phase 2, so outside it the moments h of every
   // split are constant (eval mode has no dropout; the train split's only if the moment tower has
   // no dropout-carrying hidden layer). They are computed once (refresh_moments) when the moment
   // parameters may have changed, and the phase-1/3 towers run the SDF tower only.
-  bool h_cache_ = true;                      // DLAP_H_CACHE
   bool h_valid_ = false;                     // cached h matches the current moment parameters
-  bool cache_train_h() const { return h_cache_ && (md_.nl_m == 1 || md_.dropout == 0.f); }
+  bool cache_train_h() const { return k_.h_cache && (md_.nl_m == 1 || md_.dropout == 0.f); }
   // Gram mode (k_gram.hip): while the moments are frozen the losses are quadratic forms in the
   // SDF vector, built once per moment refresh (ensure_moments). Needs the moment cache and, for
   // the conditional form, K % 4 == 0 (16-byte rows of the per-stock moment vectors).
-  bool gram_on_ = true;                      // DLAP_GRAM
-  bool gram_cond_ok() const { return gram_on_ && h_cache_ && md_.K % 4 == 0; }
+  bool gram_cond_ok() const { return k_.gram && k_.h_cache && md_.K % 4 == 0; }
   bool gram_train(int phase) const {
-    return gram_on_ && h_cache_ && (phase == 1 || (phase == 3 && cache_train_h() && gram_cond_ok()));
+    return k_.gram && k_.h_cache && (phase == 1 || (phase == 3 && cache_train_h() && gram_cond_ok()));
   }
   bool gram_eval() const { return gram_cond_ok(); }
   DevBuf<double> gram_scratch_;              // split-K partials of the Gram build
   DevBuf<char> j_gram_[3];                   // Gram build jobs per split (every model)
   DevBuf<char> j_loss_gram_[4];              // phase training loss jobs in Gram mode (epoch graphs)
   bool gram_valid_[3] = {false, false, false};   // G of split s matches the cached moments
-  bool gram_run_ = false;                    // inside run_epochs (epoch graphs use Gram mode)
   bool xs_on_ = false;                       // cross-sectional sharding hooks (set_xs)
   py::object xs_hook_;
   void xs_call(const char* what, int which, hipStream_t st) {
@@ -1222,42 +1142,34 @@ class Engine {
     xs_call("sums2", which, st);
     launch_period_fwd(lj, njobs, tmax, st, store_wn, 3);
   }
-  // Dense or Gram losses per phase (plan_phase): a Gram build pays off only over enough epochs
-  int cur_phase_ = 0;                        // phase of the run being enqueued
+  // Dense or Gram losses per phase (plan_phase): a Gram build pays off only over enough epochs.
+  // The epoch passes of run_epochs follow it; the module-API steps use the dense passes.
   bool plan_tr_[4] = {true, true, true, true}, plan_ev_[4] = {true, true, true, true};
-  bool use_gram(int phase) const { return gram_run_ && gram_train(phase) && plan_tr_[phase]; }
-  bool eval_gram_now() const { return gram_run_ && gram_eval() && plan_ev_[cur_phase_]; }
+  TrainPass epoch_pass(int phase, float lr) const {
+    TrainPass tp(phase, lr);
+    tp.gram = gram_train(phase) && plan_tr_[phase];
+    return tp;
+  }
+  EvalPass eval_pass(int phase) const {
+    EvalPass ep;
+    ep.gram = gram_eval() && plan_ev_[phase];
+    return ep;
+  }
   const LossJob* loss_tab(int phase, bool gram) const {
     return gram ? as<LossJob>(j_loss_gram_[phase]) : as<LossJob>(j_loss_train_[phase]);
   }
-  // whether the training towers of a phase run the moment network (and so need its
-  // per-period bias table from the prologue)
-  // fused LSTM + training tower forward (k_mlp_fwd_rnn): the towers trail the recurrence
-  // period by period instead of starting after it (DLAP_RNN_OVERLAP=0: two launches)
   double capture_s_ = 0.0;                   // host time spent capturing / instantiating graphs
-  bool rnn_overlap_ = true;
-  bool rnn_overlap_eval_ = false;            // ... also on the evaluation branch (DLAP_RNN_OVERLAP_EVAL)
-  // the evaluation being enqueued runs alone on the GPU (the pipeline's tail, the sequential
-  // epoch): fused there in any case -- beside the training chain the spinning tower workgroups
-  // of both fused launches compete for the same CUs (profiles/r3_knobs_fused_eval.log)
-  bool eval_solo_ = false;
-  int prog_mode_ = 1;                        // DLAP_PROG_MODE (see MlpJob::prog_mode)
-  unsigned prog_limit_ = 1u << 22;           // DLAP_PROG_SPIN_LIMIT (see MlpJob::prog_limit)
-  bool fused_p2_ = false;                    // DLAP_FUSED_PHASE2: fused training forward in phase 2 too
-  // pipelined phase-1/3 epochs: the evaluation splits' recurrences run inside the fused training
-  // forward (k_mlp_fwd_rnn, ne > 0) and their input projections inside its k_proj launch
-  // (one job table: j_rnn_all_ = train jobs, then evaluation jobs); DLAP_EVAL_IN_FWD=0: the
-  // evaluation branch runs its own prologue beside the training chain (the round-4 graph)
-  bool eval_in_fwd_ = true;
-  bool self_proj_ = true;                    // DLAP_SELF_PROJ: recurrences project their own inputs
-  DevBuf<char> j_rnn_all_;
-  int cap_all_ = 0;                          // co-residency capacity at the longest split's LDS
+  double host_launch_s_ = 0.0;               // host time in the pipelined body launches ...
+  long host_launch_n_ = 0;                   // ... over this many epochs (fused_info)
+  DevBuf<char> j_rnn_all_;                   // train jobs, then evaluation jobs (eval_in_fwd)
   DevBuf<int> prog_;
-  DevBuf<int> esync_;                        // see split_graphs()
+  DevBuf<int> esync_;                        // split epoch graphs: evaluation recurrences done / consumed
   // Co-residency guarantee of the fused LSTM + tower launches: resident workgroups of the fused
   // kernel on the device (occupancy query, rebuild_jobs) for the train split / the evaluation
-  // splits; DLAP_FUSED_CAP overrides (tests of the fallback).
-  int cap_train_ = 0, cap_eval_ = 0;
+  // splits / the longest split's LDS; DLAP_FUSED_CAP overrides (tests of the fallback).
+  int cap_train_ = 0, cap_eval_ = 0, cap_all_ = 0;
+  int tail_cap_ = 0;                         // k_lstm_tail workgroups resident at once (rebuild_jobs)
+  PhasePlan plan_[4];                        // [1..3], rebuild_jobs ([0]: nothing fused)
   // grid of a fused launch of njobs jobs wanting `want` tower workgroups each: capped so that
   // (1 + gx) * njobs workgroups are all resident at once; 0 = does not fit (two launches then)
   static int fused_grid(int want, int njobs, int cap) {
@@ -1267,45 +1179,96 @@ class Engine {
   }
   int eval_grid() const {
     int gx = std::max(gx_fwd_[1], gx_fwd_[2]);
-    if (eval_gx_ > 0) gx = std::min(gx, eval_gx_);
+    if (k_.eval_gx > 0) gx = std::min(gx, k_.eval_gx);
     return gx;
   }
   int train_fwd_grid(int phase) const { return phase == 2 ? gx_fwd_[0] : gx_fwd13_; }
-  bool fused_eval() const {
-    return rnn_overlap_ && (rnn_overlap_eval_ || eval_solo_ || eval_sep_now_) && md_.nrnn > 0 && !md_.md.wide &&
-           n_eval_jobs_ > 0 &&
-           mlp_fwd_rnn_supported(md_.md, md_.KS1, md_.WMB, md_.H, md_.nrnn, tmax_eval_) &&
-           fused_grid(eval_grid(), n_eval_jobs_, cap_eval_) > 0;
+  // evaluation recurrences per model inside the fused training forward
+  int ne_per_model() const { return G_ > 0 && n_eval_jobs_ % G_ == 0 ? n_eval_jobs_ / G_ : 0; }
+  int tmax_fwd_all() const { return std::max(splits_[0].T, tmax_eval_); }
+  bool fused_eval(const EvalPass& ep) const {
+    return (k_.rnn_overlap_eval || ep.solo || ep.sep) && plan_[1].eval_fusable;
+  }
+  // The plan of every phase (see PhasePlan), from the capacities rebuild_jobs has just computed.
+  void plan_phases() {
+    const bool overlap = k_.rnn_overlap && !safe_mode_ && md_.nrnn > 0 && !md_.md.wide;
+    auto fits = [&](int T) { return mlp_fwd_rnn_supported(md_.md, md_.KS1, md_.WMB, md_.H, md_.nrnn, T); };
+    const bool have0 = splits_[0].set, packs = inv_code_.p != nullptr;
+    const int eval_gx = fused_grid(eval_grid(), n_eval_jobs_, cap_eval_), ne = ne_per_model();
+    const bool eval_fusable = overlap && n_eval_jobs_ > 0 && fits(tmax_eval_) && eval_gx > 0;
+    for (int phase = 1; phase <= 3; ++phase) {
+      PhasePlan p;
+      p.eval_gx_solo = eval_gx;
+      p.eval_fusable = eval_fusable;
+      // phases 1 / 3 only: phase 2's training forward runs on the 1024-workgroup grid, more than the
+      // GPU holds at once; that is still deadlock-free (the LSTM workgroup is dispatched first), but
+      // with two processes sharing one GPU (the gloo rehearsal) phase-2 epochs stalled until a spin
+      // wait gave up (profiles/r3_rehearsal_bench_n2_fused_phase2.log)
+      const int gx = fused_grid(train_fwd_grid(phase), G_, cap_train_);
+      p.fused_fwd = (phase != 2 || k_.fused_p2) && overlap && fits(splits_[0].T) && gx > 0;
+      p.train_gx = p.fused_fwd ? gx : 0;
+      // the recurrences project their own inputs inside the fused launch unless the towers need the
+      // moment network's per-period bias table (k_proj's other output)
+      p.selfproj = p.fused_fwd && k_.self_proj && !train_mom(phase);
+      // pipelined phase-1/3 epochs: the evaluation splits' recurrences run inside the fused training
+      // forward (ne > 0) and their input projections inside its k_proj launch; DLAP_EVAL_IN_FWD=0:
+      // the evaluation branch runs its own prologue beside the training chain (the round-4 graph)
+      const int gxa = cap_all_ > 0 && ne > 0 ? std::min(train_fwd_grid(phase), cap_all_ / G_ - 1 - ne) : 0;
+      p.eval_in_fwd = k_.eval_in_fwd && phase != 2 && ne > 0 && p.fused_fwd && fits(tmax_fwd_all()) && gxa >= 16;
+      p.all_gx = p.eval_in_fwd ? gxa : 0;
+      // Split epoch graphs with the evaluation recurrences on the evaluation queue (DLAP_EVAL_SEP):
+      // the training chain's fused forward runs the train recurrence only; the evaluation graph waits
+      // for the previous update (k_wait_gen) and runs its own fused LSTM + tower forward (the
+      // recurrences project their inputs, the towers trail the published periods). Bitwise equal to
+      // the default; measured slower on the bench panel (0.153 vs 0.142 ms steady,
+      // profiles/r6_eval_sep_ab.txt: the train-only fused forward still takes ~42 us, so it was not
+      // bound by the evaluation recurrences, and the evaluation graph's own fused launch contends
+      // with the chain) -- off by default.
+      p.sep_eval = k_.eval_sep && phase != 2 && p.fused_fwd && eval_fusable;
+      p.tail_fused = k_.fused_tail && !xs_on_ && phase != 2 && have0 && lstm_tail_supported(md_, splits_[0].T);
+      // The pipelined eval-in-forward epoch: the clip + Adam update runs in the backward tail's last
+      // blocks (k_lstm_tail, adam 2) after the evaluation branch's bookkeeping signalled, so the
+      // training chain has no join edge and no k_adam launch (the branches join at the graph end).
+      // Co-residency guard: the tail's Adam blocks spin, holding their CU slots, until the
+      // evaluation branch signals; G * nadam of them must leave at least half of the device's tail-sized
+      // slots (occupancy query, tail_cap_) to the evaluation launches they wait for, else the epoch
+      // keeps the join + k_adam update.
+      const int nadam = (md_.P_sdf + ADAM_PB - 1) / ADAM_PB;
+      p.adam_in_tail = k_.tail_adam != 0 && !safe_mode_ && p.tail_fused && packs && tail_cap_ > 0 &&
+                       2 * G_ * nadam <= tail_cap_;
+      // Split epoch graphs (the pipelined eval-in-forward epoch with the update in the tail): the
+      // training chain is one single-queue graph on st_ (fused forward -> losses -> tower backward ->
+      // tail + Adam) and the evaluation branch another on st2_ (k_wait_count -> evaluation towers ->
+      // losses -> masks -> bookkeeping), launched side by side every epoch with NO graph edge between
+      // them: the evaluation graph waits in-kernel for the fused forward's evaluation recurrences
+      // (esync_ counts), the tail's Adam blocks for the bookkeeping's signal. A cross-queue edge
+      // inside a graph costs ~5-6 us on the chain and a graph that ends on two queues ~12 us at its
+      // boundary (profiles/r5_*timeline*); these cost one poll each.
+      p.split_graphs = k_.split_graphs && !safe_mode_ && p.adam_in_tail && (p.sep_eval || p.eval_in_fwd);
+      // Phase 2: k_finalize -> k_wgrad -> k_adam and the train metrics as ONE launch (k_lstm_tail,
+      // phase 2: the per-period sums relayed to the W_macro helpers, the moment network's clip + Adam
+      // in the last blocks); the frozen SDF's LSTM recurrence once per run_epochs call
+      p.mom_tail = phase == 2 && k_.mom_tail && !xs_on_ && packs && have0 && mom_tail_supported(md_, splits_[0].T);
+      p.p2_lstm_cached = phase == 2 && k_.p2_lstm_cache && md_.nrnn > 0 && (md_.nrnn == 1 || md_.dropout == 0.f) &&
+                         !xs_on_;
+      plan_[phase] = p;
+    }
+  }
+  // (the one-graph pipelined fallback keeps the join + k_adam update unless DLAP_TAIL_ADAM=2: an
+  // in-kernel wait across the graph's two branches would rest on the runtime mapping them to
+  // different hardware queues -- ADVICE r5)
+  RunMode run_mode(int phase) const {
+    const PhasePlan& p = plan_[phase];
+    RunMode m;
+    m.pipe = phase != 2 && n_eval_jobs_ > 0 && pipeline_;
+    m.split = m.pipe && p.split_graphs;
+    m.sep = m.split && p.sep_eval;
+    m.tail_adam = m.split || (m.pipe && p.eval_in_fwd && k_.tail_adam == 2 && p.adam_in_tail);
+    return m;
   }
  public:
   double capture_seconds() const { return capture_s_; }
-  // phases 1 / 3 only: phase 2's training forward runs on the 1024-workgroup grid, more than the
-  // GPU holds at once; that is still deadlock-free (the LSTM workgroup is dispatched first), but
-  // with two processes sharing one GPU (the gloo rehearsal) phase-2 epochs stalled until a spin
-  // wait gave up (profiles/r3_rehearsal_bench_n2_fused_phase2.log)
-  bool fused_fwd(int phase) const {
-    if (phase == 2 && !fused_p2_) return false;
-    return rnn_overlap_ && md_.nrnn > 0 && !md_.md.wide &&
-           mlp_fwd_rnn_supported(md_.md, md_.KS1, md_.WMB, md_.H, md_.nrnn, splits_[0].T) &&
-           fused_grid(train_fwd_grid(phase), G_, cap_train_) > 0;
-  }
-  // the capped grids of the fused launches (valid when fused_fwd / fused_eval)
-  int fused_train_gx(int phase) const { return fused_grid(train_fwd_grid(phase), G_, cap_train_); }
-  int fused_eval_gx() const { return fused_grid(eval_grid(), n_eval_jobs_, cap_eval_); }
-  // evaluation recurrences per model inside the fused training forward, and its grid
-  int ne_per_model() const { return G_ > 0 && n_eval_jobs_ % G_ == 0 ? n_eval_jobs_ / G_ : 0; }
-  int tmax_fwd_all() const { return std::max(splits_[0].T, tmax_eval_); }
-  int fused_all_gx(int phase) const {
-    const int ne = ne_per_model();
-    if (cap_all_ <= 0 || ne <= 0) return 0;
-    const int gx = std::min(train_fwd_grid(phase), cap_all_ / G_ - 1 - ne);
-    return gx >= 16 ? gx : 0;
-  }
-  bool eval_rnn_in_fwd(int phase) const {
-    if (!eval_in_fwd_ || phase == 2 || n_eval_jobs_ == 0 || ne_per_model() == 0 || !fused_fwd(phase)) return false;
-    if (!mlp_fwd_rnn_supported(md_.md, md_.KS1, md_.WMB, md_.H, md_.nrnn, tmax_fwd_all())) return false;
-    return fused_all_gx(phase) > 0;
-  }
+  bool fused_fwd(int phase) const { return phase >= 1 && phase <= 3 && plan_[phase].fused_fwd; }
   // zero the spin-timeout counters (tests: the device poison is permanent otherwise)
   void reset_prog_errors() {
     sync();
@@ -1322,23 +1285,24 @@ class Engine {
   }
   py::dict fused_info() const {
     py::dict d;
+    const RunMode m = run_mode(1);
     d["cap_train"] = cap_train_; d["cap_eval"] = cap_eval_;
-    for (int ph = 1; ph <= 3; ++ph) d[("train_gx_p" + std::to_string(ph)).c_str()] = fused_fwd(ph) ? fused_train_gx(ph) : 0;
-    d["eval_gx_solo"] = fused_grid(eval_grid(), n_eval_jobs_, cap_eval_);
+    for (int ph = 1; ph <= 3; ++ph) d[("train_gx_p" + std::to_string(ph)).c_str()] = plan_[ph].train_gx;
+    d["eval_gx_solo"] = plan_[1].eval_gx_solo;
     // pipelined epochs with the evaluation recurrences inside the fused training forward
     d["cap_all"] = cap_all_;
     d["tail_cap"] = tail_cap_;
     for (int ph = 1; ph <= 3; ph += 2) {
-      d[("eval_in_fwd_p" + std::to_string(ph)).c_str()] = eval_rnn_in_fwd(ph);
-      d[("all_gx_p" + std::to_string(ph)).c_str()] = eval_rnn_in_fwd(ph) ? fused_all_gx(ph) : 0;
+      d[("eval_in_fwd_p" + std::to_string(ph)).c_str()] = plan_[ph].eval_in_fwd;
+      d[("all_gx_p" + std::to_string(ph)).c_str()] = plan_[ph].all_gx;
     }
     d["eval_per_model"] = ne_per_model();
-    d["fused_tail"] = tail_fused(1);
-    d["mom_tail"] = mom_tail_on(2);
-    d["p2_lstm_cached"] = p2_lstm_cached();
-    d["adam_in_tail"] = adam_in_tail(1) && pipeline_ && eval_rnn_in_fwd(1) && (split_graphs(1) || tail_adam_pipe_);
-    d["split_graphs"] = split_graphs(1) && pipeline_;
-    d["eval_sep"] = split_graphs(1) && pipeline_ && sep_eval(1);
+    d["fused_tail"] = plan_[1].tail_fused;
+    d["mom_tail"] = plan_[2].mom_tail;
+    d["p2_lstm_cached"] = plan_[2].p2_lstm_cached;
+    d["adam_in_tail"] = m.tail_adam && plan_[1].eval_in_fwd;   // (of the eval-in-forward epoch)
+    d["split_graphs"] = m.split;
+    d["eval_sep"] = m.sep;
     d["host_launch_us_per_epoch"] = host_launch_n_ ? 1e6 * host_launch_s_ / host_launch_n_ : 0.0;
     // backward launch shape: fine slabs per model (R-only partition), fine slabs per workgroup
     d["bwd_nfine"] = nfine_; d["bwd_fpw"] = fpw_;
@@ -1395,6 +1359,9 @@ class Engine {
   bool pipeline_ = true;
   // uint16 elements per panel / blob value: 1 (bf16) or 2 (fp32 reference-precision towers)
   long xw() const { return md_.md.fp32 ? 2 : 1; }
+  static void check_phase(int phase) {        // (the per-phase job tables and plans are [1..3])
+    if (phase < 1 || phase > 3) throw std::invalid_argument("phase must be 1, 2 or 3");
+  }
   int check_g(int g) const {
     if (g < 0 || g >= G_) throw std::out_of_range("model index");
     return g;
@@ -1445,7 +1412,7 @@ class Engine {
     const int ks = (F + ppw + 31) / 32;
     // wide path: layer-0 inputs beyond the 128 columns a fused tower tile holds in registers
     // (or DLAP_WIDE=1) -> layer 0 runs as the streaming k_proj0 / k_wgrad0 GEMMs
-    const bool wide = ks > 4 || env_int("DLAP_WIDE", 0) != 0;
+    const bool wide = ks > 4 || k_.wide;
     if (wide) {
       d.KS1 = 2;                                    // template slot of the ZIN tower kernels
       d.KSB = 0;                                    // no layer-0 fragments in the tower blob
@@ -1529,12 +1496,11 @@ class Engine {
     // one gradient tile per slice (the slices recompute the forward each, but the kernel fits
     // two waves per SIMD: DLAP_BWD1_WPS) measured faster than two tiles sharing one recompute at
     // one wave per SIMD (profiles/r4_bwd_shape.log); DLAP_TPS=2 selects the latter
-    const char* tps_env = std::getenv("DLAP_TPS");
-    const bool tps2 = (wide || d.KS1 == 2) && d.ntile_s == 2 && tps_env && std::atoi(tps_env) == 2;
+    const bool tps2 = (wide || d.KS1 == 2) && d.ntile_s == 2 && k_.tps == 2;
     d.tps_s = tps2 ? 2 : 1;
     // the one-pass backward (k_tbwd.hip) where it is instantiated: every gradient tile in one
     // slice, the wide path included (DLAP_TBWD=0: the sliced kernel, kept for the fp32 / wide-row shapes)
-    d.tbwd = (env_int("DLAP_TBWD", 1) != 0 && tbwd_supported(D, d.KS1) && d.ntile_s == d.nl_s) ? 1 : 0;
+    d.tbwd = (k_.tbwd && tbwd_supported(D, d.KS1) && d.ntile_s == d.nl_s) ? 1 : 0;
     if (d.tbwd) d.tps_s = d.ntile_s;
     // at least one slice: slice 0 also produces the bias / output / per-period gradients
     d.nslice_s = std::max(1, (d.ntile_s + d.tps_s - 1) / d.tps_s);
@@ -1615,19 +1581,14 @@ class Engine {
       // order is the same whether a model trains alone or batched with others (VERDICT r3
       // item 1). The launch shape (fine slabs per workgroup) is chosen in rebuild_jobs.
       const int ntiles = (R + 31) / 32;
-      const int ncoarse = std::max(1, std::min(env_int("DLAP_NSLAB_COARSE", 64), ((ntiles + 3) / 4 + 3) / 4));
+      const int ncoarse = std::max(1, std::min(k_.nslab_coarse, ((ntiles + 3) / 4 + 3) / 4));
       nfine_ = 4 * ncoarse;
       const int nsl = std::max(md_.nslice_s, md_.nslice_m);
       slab_.alloc((size_t)G_ * nsl * nfine_ * slab_stride());
     }
-    // tower-forward grids (measured, 600x3000x46 epoch graph): the phase-1/3 training forward
-    // runs SDF-only (moments cached) beside the evaluation branch and is fastest with one
-    // workgroup per CU (256); phase 2 (moment tower, no evaluation branch) with 1024
-    gx_fwd_[s] = std::max(1, std::min(((R + 31) / 32 + 3) / 4,
-                                      env_int("DLAP_GX_FWD", G_ <= 2 ? 1024 : grid_per_model(1024, 128, G_))));
-    if (s == 0) {
-      gx_fwd13_ = std::max(1, std::min(((R + 31) / 32 + 3) / 4, env_int("DLAP_GX_FWD13", grid_per_model(384, 96, G_))));
-    }
+    // tower-forward grids: the tuned ones (Knobs::gx_fwd / gx_fwd13), at most a workgroup per 4 tiles
+    gx_fwd_[s] = std::max(1, std::min(((R + 31) / 32 + 3) / 4, k_.gx_fwd));
+    if (s == 0) gx_fwd13_ = std::max(1, std::min(((R + 31) / 32 + 3) / 4, k_.gx_fwd13));
     if (md_.md.wide) {
       const size_t ntl = (size_t)(R + 31) / 32;
       for (int g = 0; g < G_; ++g) {
@@ -1640,17 +1601,17 @@ class Engine {
       }
       if (s == 0) {
         // split-K of the layer-0 weight gradient: ~8 tiles per workgroup, at most 2 per CU
-        nsplit_ = std::max(1, std::min((int)((ntl + 7) / 8), env_int("DLAP_WG_SPLIT", 512)));
+        nsplit_ = std::max(1, std::min((int)((ntl + 7) / 8), k_.wg_split));
         for (int g = 0; g < G_; ++g) ws(g, 0).wpart.alloc(wide_part_floats(md_.md, md_.WMB, nsplit_), false);
       }
-      gx_proj_[s] = std::max(1, std::min((int)((ntl + 3) / 4), env_int("DLAP_GX_PROJ", 512)));
+      gx_proj_[s] = std::max(1, std::min((int)((ntl + 3) / 4), k_.gx_proj));
     }
     // per-period SDF inputs [T][Dm] are staged in LDS by the tower kernels when small
     int tmax = 0;
     for (int k = 0; k < 3; ++k)
       if (splits_[k].set || k == s) tmax = std::max(tmax, splits_[k].T);
     const int ppf = tmax * md_.md.ppst;
-    md_.md.pp_lds_floats = (md_.Dm > 0 && ppf <= 8192 && !env_int("DLAP_PP_GLOBAL", 0)) ? ppf : 0;
+    md_.md.pp_lds_floats = (md_.Dm > 0 && ppf <= 8192 && !k_.pp_global) ? ppf : 0;
   }
 
   // ------------------------------------------------------------ job tables ------------
@@ -1680,7 +1641,7 @@ class Engine {
   // tables that launch it (training split: train tables; evaluation splits: the eval tables)
   int* prog_ptr(int g, int s) { return prog_.p + 16 * (3 * g + s); }
   void set_prog(MlpJob& J, int g, int s) {
-    J.prog = prog_ptr(g, s); J.prog_err = prog_ptr(g, s) + 1; J.prog_mode = prog_mode_; J.prog_limit = prog_limit_;
+    J.prog = prog_ptr(g, s); J.prog_err = prog_ptr(g, s) + 1; J.prog_mode = k_.prog_mode; J.prog_limit = k_.spin_limit;
   }
   const float* pp_ptr(int g, int s) {
     if (md_.nrnn > 0) return ws(g, s).pp.p;
@@ -1804,26 +1765,26 @@ class Engine {
   // Build the Gram matrices of every (model, split) from the current cached moments.
   // Stream-ordered on st_ (no host synchronisation). defer: the evaluation splits' builds go
   // to the evaluation stream st2_ (after the moment refresh queued so far) and
-  // eval_gram_pending_ is set: the caller joins ev_gram_ into st_ before the first graph that
-  // evaluates (the pipelined head trains only, so they overlap it).
-  void build_gram(bool defer = false, int smask = 7) {
+  // eval_gram_pending_ is set: the caller joins ev_[EV_GRAM] into st_ before the first graph that
+  // evaluates (the pipelined head trains only, so they overlap it). phase 1..3: only what that
+  // phase's plan reads (run_epochs); 0: every split's matrices.
+  void build_gram(int phase, bool defer = false, int smask = 7) {
     bool forked = false;
     for (int s = 0; s < 3; ++s) {
       if (!((smask >> s) & 1)) continue;
       const SplitDev& D = splits_[s];
       if (!D.set || D.T == 0 || gram_valid_[s]) continue;
-      // only what the current run's plan reads (run_epochs sets cur_phase_; 0: everything)
-      if (cur_phase_ >= 1 && cur_phase_ <= 3 && !(s == 0 ? plan_tr_[cur_phase_] : plan_ev_[cur_phase_])) continue;
+      if (phase >= 1 && phase <= 3 && !(s == 0 ? plan_tr_[phase] : plan_ev_[phase])) continue;
       gram_valid_[s] = true;
       hipStream_t st = st_;
-      if ((s > 0 || train_gram_side_) && defer) {
+      if ((s > 0 || k_.train_gram_side) && defer) {
         // the builds read the cached moments: st2_ waits for everything queued on st_ so far --
         // on the wide path the moment refresh itself runs on st_ (ensure_moments), so a build
         // deferred while an earlier one is still pending must fork again, or it reads moments
         // the refresh is still writing (run-to-run differences, profiles/r6_wide_determinism.txt)
         if (!forked) {
-          HIP_OK(hipEventRecord(ev_fork_, st_));
-          HIP_OK(hipStreamWaitEvent(st2_, ev_fork_, 0));
+          HIP_OK(hipEventRecord(ev_[EV_FORK], st_));
+          HIP_OK(hipStreamWaitEvent(st2_, ev_[EV_FORK], 0));
           forked = true;
         }
         if (s > 0) eval_gram_pending_ = true;
@@ -1833,41 +1794,33 @@ class Engine {
       launch_gram(as<GramJob>(j_gram_[s]), G_, D.T, gram_slices(D.T), st);
       xs_call("gram", 1 << s, st);         // sharded: G summed over every rank's stocks
       if (s == 0 && st == st2_) {
-        HIP_OK(hipEventRecord(ev_trgram_, st2_));
+        HIP_OK(hipEventRecord(ev_[EV_TRGRAM], st2_));
         train_gram_pending_ = true;
       }
     }
-    if (eval_gram_pending_) HIP_OK(hipEventRecord(ev_gram_, st2_));
+    if (eval_gram_pending_) HIP_OK(hipEventRecord(ev_[EV_GRAM], st2_));
   }
   // st_ waits for the train split's deferred refresh + Gram build (no-op when none is pending)
   void join_train_gram() {
     if (!train_gram_pending_) return;
-    HIP_OK(hipStreamWaitEvent(st_, ev_trgram_, 0));
+    HIP_OK(hipStreamWaitEvent(st_, ev_[EV_TRGRAM], 0));
     train_gram_pending_ = false;
   }
-  bool train_gram_side_ = false;             // DLAP_TRAIN_GRAM_SIDE
-  bool train_gram_pending_ = false;
-  hipEvent_t ev_trgram_ = nullptr;
-  int tg_part_ = 0;                          // enqueue_train_grads: 1 forward only, 2 the rest
   // The head epoch of a pipelined run. With the train split's moment refresh / Gram build deferred
   // to the evaluation stream, two graphs: the forward (dropout masks, LSTM + towers) overlaps the
   // build, then st_ waits for it and the losses, backward and update follow.
   void launch_head(int phase, float lr, int ig, float sel) {
     if (!train_gram_pending_) {
-      hipGraphExec_t head = graph_for(graph_key(phase, lr, ig, sel, 1), [&] { enqueue_head(phase, lr); });
+      hipGraphExec_t head = graph_for(graph_key(phase, lr, ig, sel, 1), [&] { enqueue_head(phase, lr, 0); });
       HIP_OK(hipGraphLaunch(head, st_));
       return;
     }
     hipGraphExec_t a = graph_for(graph_key(phase, lr, ig, sel, 11), [&] {
-      tg_part_ = 1;
-      enqueue_train_grads(phase);
-      tg_part_ = 0;
+      TrainPass tp = epoch_pass(phase, lr);
+      tp.part = 1;
+      enqueue_train_grads(tp);
     });
-    hipGraphExec_t b = graph_for(graph_key(phase, lr, ig, sel, 12), [&] {
-      tg_part_ = 2;
-      enqueue_head(phase, lr);
-      tg_part_ = 0;
-    });
+    hipGraphExec_t b = graph_for(graph_key(phase, lr, ig, sel, 12), [&] { enqueue_head(phase, lr, 2); });
     HIP_OK(hipGraphLaunch(a, st_));
     join_train_gram();
     HIP_OK(hipGraphLaunch(b, st_));
@@ -1875,7 +1828,7 @@ class Engine {
   // st_ waits for deferred evaluation-split Gram builds (no-op when none is pending)
   void join_eval_gram() {
     if (!eval_gram_pending_) return;
-    HIP_OK(hipStreamWaitEvent(st_, ev_gram_, 0));
+    HIP_OK(hipStreamWaitEvent(st_, ev_[EV_GRAM], 0));
     eval_gram_pending_ = false;
   }
 
@@ -1902,7 +1855,7 @@ class Engine {
         // k_finalize) if the images fit without losing a workgroup per CU -- measured slower at
         // G = 3 and 9 (the runtime slab loop spills more and every fine slab still pays its
         // reduction: 10.58k vs 10.72k model-epochs/s at G = 9, profiles/r4_bwd_shape.log)
-      const int want = env_int("DLAP_BWD_FPW", 1);
+      const int want = k_.bwd_fpw;
       const int tps = std::max(md_.tps_s, md_.tps_m);
       fpw_ = (want == 4 && !md_.tbwd && mlp_bwd_fpw_fits(md_.md, md_.KS1, slab_stride(), tps, 4)) ? 4 : 1;
       gx_bwd_ = nfine_ / fpw_;
@@ -1919,10 +1872,10 @@ class Engine {
       for (int s = 1; s < 3; ++s) {
         if (!splits_[s].set) continue;
         re.push_back(rnn_job(g, s, false));
-        me.push_back(mlp_job(g, s, false, true, !h_cache_));
+        me.push_back(mlp_job(g, s, false, true, !k_.h_cache));
         re.back().prog = prog_ptr(g, s);
         set_prog(me.back(), g, s);
-        we.push_back(wide_job(g, s, true, !h_cache_));
+        we.push_back(wide_job(g, s, true, !k_.h_cache));
         le.push_back(loss_job(g, s, 0, gram_eval()));
         led.push_back(loss_job(g, s, 0, false));
         tmax_eval_ = std::max(tmax_eval_, splits_[s].T);
@@ -1949,7 +1902,7 @@ class Engine {
       U.T = splits_[0].T; U.seed = S.seed; U.lr = S.lr; U.prog = prog_ptr(g, 0); U.dropout = S.dropout;
       U.inv_code = inv_code_.p; U.upd_ctr = S.upd_ctr.p;
       if (splits_[0].set && (S.mscr.n < (size_t)splits_[0].T * 64)) S.mscr.alloc((size_t)std::max(splits_[0].T, 1) * 64, false);
-      U.tail_ctr = S.tail_ctr.p; U.mscr = S.mscr.p; U.spin_limit = prog_limit_;
+      U.tail_ctr = S.tail_ctr.p; U.mscr = S.mscr.p; U.spin_limit = k_.spin_limit;
       uj.push_back(U);
     }
     n_eval_jobs_ = (int)le.size();
@@ -1959,8 +1912,8 @@ class Engine {
       upload(j_rnn_all_, ra);
     }
     {   // co-residency capacity of the fused launches (no GPU query when they cannot run)
-      const int force = env_int("DLAP_FUSED_CAP", -1);
-      const bool can = rnn_overlap_ && md_.nrnn > 0 && !md_.md.wide;
+      const int force = k_.fused_cap;
+      const bool can = k_.rnn_overlap && !safe_mode_ && md_.nrnn > 0 && !md_.md.wide;
       cap_train_ = !can || !splits_[0].set ? 0
                    : force >= 0 ? force : mlp_fwd_rnn_capacity(md_.md, md_.KS1, md_.WMB, md_.H, md_.nrnn, splits_[0].T);
       cap_eval_ = !can || n_eval_jobs_ == 0 ? 0
@@ -1968,7 +1921,8 @@ class Engine {
       cap_all_ = !can || n_eval_jobs_ == 0 || !splits_[0].set ? 0
                  : force >= 0 ? force : mlp_fwd_rnn_capacity(md_.md, md_.KS1, md_.WMB, md_.H, md_.nrnn, tmax_fwd_all());
     }
-    if (gram_on_) build_gram_jobs();
+    plan_phases();
+    if (k_.gram) build_gram_jobs();
     for (bool& v : gram_valid_) v = false;
     upload(j_rnn_train_, rt); upload(j_rnn_eval_, re); upload(j_mlp_eval_, me); upload(j_loss_eval_, le); upload(j_loss_eval_dense_, led);
     upload(j_fin_, fj); upload(j_upd_, uj); upload(j_wide_eval_, we);
@@ -2053,42 +2007,43 @@ class Engine {
 
   // Recompute the cached moments of every split (enqueued on st_, ahead of the epochs that
   // read them) if the moment parameters may have changed since they were computed.
-  // with_gram: also (re)build the Gram matrices (epoch graphs: run_epochs); the module-API
-  // steps use the dense loss passes and skip it.
-  void ensure_moments(bool with_gram = false, bool defer_eval_gram = false) {
-    if (!h_cache_ || n_mom_jobs_ == 0) return;
+  // gram_phase >= 0: also (re)build the Gram matrices that phase's plan reads (epoch graphs:
+  // run_epochs; 0: all of them); the module-API steps use the dense loss passes and skip it.
+  void ensure_moments(int gram_phase = -1, bool defer_eval_gram = false) {
+    const bool with_gram = gram_phase >= 0 && k_.gram;
+    if (!k_.h_cache || n_mom_jobs_ == 0) return;
     if (h_valid_) {
-      if (with_gram && gram_on_) build_gram(defer_eval_gram);
+      if (with_gram) build_gram(gram_phase, defer_eval_gram);
       return;
     }
     HTRACE("ensure_moments jobs=%d tmax=%d gx=%d", n_mom_jobs_, tmax_all_, gx_mom_);
     const int n_ev = n_mom_jobs_ - n_mom_tr_;
-    if (defer_eval_gram && gram_on_ && !md_.md.wide && n_mom_tr_ > 0 && n_ev > 0) {
+    if (defer_eval_gram && k_.gram && !md_.md.wide && n_mom_tr_ > 0 && n_ev > 0) {
       // the evaluation splits' moments (and then their Gram builds, build_gram) on the
       // evaluation stream: only the train split's refresh + Gram precede the head epoch (which
       // trains only); the first graph that evaluates joins them (join_eval_gram)
-      HIP_OK(hipEventRecord(ev_fork_, st_));
-      HIP_OK(hipStreamWaitEvent(st2_, ev_fork_, 0));
+      HIP_OK(hipEventRecord(ev_[EV_FORK], st_));
+      HIP_OK(hipStreamWaitEvent(st2_, ev_[EV_FORK], 0));
       eval_gram_pending_ = true;
       HTRACE("launch_prologue (moments, split)");
-      // (train_gram_side_: the train split's refresh and Gram build too, ahead of the evaluation
+      // (DLAP_TRAIN_GRAM_SIDE: the train split's refresh and Gram build too, ahead of the evaluation
       // splits' -- the head epoch's forward needs neither, its loss pass waits, launch_head)
-      hipStream_t sm = train_gram_side_ ? st2_ : st_;
+      hipStream_t sm = k_.train_gram_side ? st2_ : st_;
       launch_prologue(as<RnnJob>(j_rnn_mom_), n_mom_tr_, tmax_mom_tr_, dd(), md_, sm, true, false);
       launch_mlp_fwd(as<MlpJob>(j_mlp_mom_), n_mom_tr_, gx_mom_, md_.md, md_.KS1, md_.WMB, sm);
       for (bool& v : gram_valid_) v = false;
-      if (train_gram_side_) build_gram(true, 1);          // (the head's loss pass waits for it first)
+      if (k_.train_gram_side) build_gram(gram_phase, true, 1);          // (the head's loss pass waits for it first)
       launch_prologue(as<RnnJob>(j_rnn_mom_) + n_mom_tr_, n_ev, tmax_mom_ev_, dd(), md_, st2_, true, false);
       launch_mlp_fwd(as<MlpJob>(j_mlp_mom_) + n_mom_tr_, n_ev, gx_mom_, md_.md, md_.KS1, md_.WMB, st2_);
       h_valid_ = true;
-      build_gram(true);
+      build_gram(gram_phase, true);
       return;
     }
     HTRACE("launch_prologue");
     launch_prologue(as<RnnJob>(j_rnn_mom_), n_mom_jobs_, tmax_all_, dd(), md_, st_, true, false);
-    if (md_.md.wide && zx_eval_) {
+    if (md_.md.wide && k_.zx_eval) {
       HTRACE("launch_mlp_fwd_zx");
-      launch_mlp_fwd_zx(as<MlpJob>(j_mlp_mom_), n_mom_jobs_, std::max(1, zx_gx_ / n_mom_jobs_), md_.md, md_.WMB, st_);
+      launch_mlp_fwd_zx(as<MlpJob>(j_mlp_mom_), n_mom_jobs_, std::max(1, k_.zx_gx / n_mom_jobs_), md_.md, md_.WMB, st_);
     } else {
       if (md_.md.wide) launch_proj0(as<WideJob>(j_wide_mom_), n_mom_jobs_, std::max({gx_proj_[0], gx_proj_[1], gx_proj_[2]}),
                                     md_.md, md_.WMB, st_);
@@ -2097,7 +2052,7 @@ class Engine {
     }
     h_valid_ = true;
     for (bool& v : gram_valid_) v = false;
-    if (with_gram && gram_on_) build_gram(defer_eval_gram);
+    if (with_gram) build_gram(gram_phase, defer_eval_gram);
   }
   bool dropmask_on(int phase) const { return md_.dropout > 0.f && phase != 2; }
   // keep masks of the step *drop_step + offset* (phases 1/3: the SDF tower's dropout)
@@ -2106,58 +2061,48 @@ class Engine {
     HTRACE("launch_dropmask");
     launch_dropmask(as<MlpJob>(j_mlp_train_[phase]), G_, (splits_[0].R + 31) / 32, md_.md, offset, st);
   }
-  // premasked: this step's keep masks were generated by the previous epoch graph.
-  // mark: record ev_a_ after the tower forward (2);
-  // defer_metrics: the train split's metrics are left to the caller (it records ev_mid_ after the
-  // asset pass; the pipelined epoch runs them on the evaluation branch, off the critical chain).
-  // eval_rnn: the evaluation splits' projections and recurrences ride in the training prologue
-  // and fused forward (eval_rnn_in_fwd; the caller's evaluation branch starts at its towers)
-  void enqueue_train_grads(int phase, bool premasked = false, int mark = 0, bool defer_metrics = false,
-                           bool eval_rnn = false) {
+  // The training forward of a pass: masks -> projection / prologue -> proj0 / fwd_zx / fused / plain towers
+  void enqueue_train_fwd(const TrainPass& tp) {
+    const int phase = tp.phase;
     const SplitDev& D = splits_[0];
-    const bool gram = use_gram(phase);
-    const LossJob* lj = loss_tab(phase, gram);
-    // (tg_part_: the head epoch split around the wait for a deferred train Gram build, launch_head)
-    if (tg_part_ != 2) {
-    if (!premasked) enqueue_dropmask(phase, 0, st_);
+    const PhasePlan& P = plan_[phase];
+    if (!tp.premasked) enqueue_dropmask(phase, 0, st_);
     // the latency-bound LSTM first, before the streaming projection loads the memory system
     // (fused: only its input projection here, the recurrence runs inside the tower launch)
-    const bool fused = fused_fwd(phase);
-    // the recurrences project their own inputs inside the fused launch unless the towers need the
-    // moment network's per-period bias table (k_proj's other output)
-    const bool selfproj = fused && self_proj_ && !train_mom(phase) && !md_.md.wide;
-    HTRACE("launch_prologue fused=%d eval_rnn=%d selfproj=%d", (int)fused, (int)eval_rnn, (int)selfproj);
+    const bool fused = P.fused_fwd, selfproj = P.selfproj && tp.own_proj;
+    HTRACE("launch_prologue fused=%d eval_rnn=%d selfproj=%d", (int)fused, (int)tp.eval_rnn, (int)selfproj);
     if (selfproj) {}
-    else if (eval_rnn) launch_proj(as<RnnJob>(j_rnn_all_), G_ + n_eval_jobs_, tmax_fwd_all(), dd(), md_, st_, train_mom(phase));
+    else if (tp.eval_rnn) launch_proj(as<RnnJob>(j_rnn_all_), G_ + n_eval_jobs_, tmax_fwd_all(), dd(), md_, st_, train_mom(phase));
     else if (fused) launch_proj(as<RnnJob>(j_rnn_train_), G_, D.T, dd(), md_, st_, train_mom(phase));
-    else if (phase == 2 && lstm_once_) launch_prologue(as<RnnJob>(j_rnn_train_), G_, D.T, dd(), md_, st_, true, false);
+    else if (phase == 2 && tp.lstm_once) launch_prologue(as<RnnJob>(j_rnn_train_), G_, D.T, dd(), md_, st_, true, false);
     else launch_prologue(as<RnnJob>(j_rnn_train_), G_, D.T, dd(), md_, st_, train_mom(phase));
-    // pipelined epoch, train_first_ == 2: the evaluation branch's LSTM prologue is enqueued right
-    // behind the training one, so its (serial, few-CU) recurrence starts at the epoch start
-    // instead of behind every training-chain node of the graph
-    if (eval_prologue_hook_) { enqueue_eval_prologue(eval_prologue_hook_); eval_prologue_hook_ = nullptr; }
-    const bool zx_train = md_.md.wide && zx_train_;
+    if (tp.eval_prologue) enqueue_eval_prologue(tp.eval_prologue, EvalPass());
+    const bool zx_train = md_.md.wide && k_.zx_train;
     if (md_.md.wide && !zx_train)
       launch_proj0(as<WideJob>(j_wide_train_[phase]), G_, gx_proj_[0], md_.md, md_.WMB, st_);
     if (zx_train)      // layer 0 streamed inside the training towers, z stored for the backward
-      launch_mlp_fwd_zx(as<MlpJob>(j_mlp_train_[phase]), G_, std::max(1, zx_gx_ / G_), md_.md, md_.WMB, st_, true);
-    else if (eval_rnn)
-      launch_mlp_fwd_rnn(as<MlpJob>(j_mlp_train_[phase]), as<RnnJob>(j_rnn_all_), dd(), G_, fused_all_gx(phase),
+      launch_mlp_fwd_zx(as<MlpJob>(j_mlp_train_[phase]), G_, std::max(1, k_.zx_gx / G_), md_.md, md_.WMB, st_, true);
+    else if (tp.eval_rnn)
+      launch_mlp_fwd_rnn(as<MlpJob>(j_mlp_train_[phase]), as<RnnJob>(j_rnn_all_), dd(), G_, P.all_gx,
                          md_.md, md_.KS1, md_.WMB, md_.H, md_.nrnn, tmax_fwd_all(), st_, !train_mom(phase),
-                         ne_per_model(), selfproj, fwd_esig_);
+                         ne_per_model(), selfproj, tp.esig);
     else if (fused)
-      launch_mlp_fwd_rnn(as<MlpJob>(j_mlp_train_[phase]), as<RnnJob>(j_rnn_train_), dd(), G_,
-                         fused_train_gx(phase), md_.md, md_.KS1, md_.WMB, md_.H, md_.nrnn, D.T, st_,
-                         !train_mom(phase), 0, selfproj);
+      launch_mlp_fwd_rnn(as<MlpJob>(j_mlp_train_[phase]), as<RnnJob>(j_rnn_train_), dd(), G_, P.train_gx,
+                         md_.md, md_.KS1, md_.WMB, md_.H, md_.nrnn, D.T, st_, !train_mom(phase), 0, selfproj);
     else
-      launch_mlp_fwd(as<MlpJob>(j_mlp_train_[phase]), G_, phase == 2 ? gx_fwd_[0] : gx_fwd13_, md_.md, md_.KS1,
-                     md_.WMB, st_, !train_mom(phase));
-    if (mark == 2) HIP_OK(hipEventRecord(ev_a_, st_));
-    }
-    if (tg_part_ == 1) return;
+      launch_mlp_fwd(as<MlpJob>(j_mlp_train_[phase]), G_, train_fwd_grid(phase), md_.md, md_.KS1, md_.WMB, st_,
+                     !train_mom(phase));
+    if (tp.mark_fwd) HIP_OK(hipEventRecord(ev_[EV_FWD], st_));
+  }
+  void enqueue_train_grads(const TrainPass& tp) {
+    const int phase = tp.phase;
+    const SplitDev& D = splits_[0];
+    const LossJob* lj = loss_tab(phase, tp.gram);
+    if (tp.part != 2) enqueue_train_fwd(tp);
+    if (tp.part == 1) return;
     HTRACE("launch_period_fwd");
     period_fwd(lj, G_, D.T, st_, false, 1);
-    if (!gram) {
+    if (!tp.gram) {
       if (xs_on_ && phase != 2)
         throw std::runtime_error("sharded engine: phases 1 / 3 need the Gram-form losses (K % 4 == 0, cached moments)");
       HTRACE("launch_asset");
@@ -2169,10 +2114,10 @@ class Engine {
       HTRACE("launch_period_bwd(gram)");
       launch_period_bwd(lj, G_, D.T, st_);
     }
-    if ((tail_metrics_ && phase != 2) || mom_tail(phase)) {
+    if ((tp.tail_metrics && phase != 2) || tp.mom_adam) {
       // the train split's metrics are computed by the backward tail (enqueue_train_tail)
-    } else if (defer_metrics && phase != 2) {
-      HIP_OK(hipEventRecord(ev_mid_, st_));
+    } else if (tp.defer_metrics && phase != 2) {
+      HIP_OK(hipEventRecord(ev_[EV_MID], st_));
     } else {
       // (k_job_metrics, not the metrics workgroup of k_period_bwd<true>: the same reduction
       // order as the deferred launch of the pipelined epochs, so both schedules are bitwise equal)
@@ -2184,7 +2129,7 @@ class Engine {
       launch_mlp_bwd_mom(as<MlpJob>(j_mlp_bwd_[phase]), G_, gx_bwd_, md_.nslice_m, 1, md_.md, md_.KS1,
                          md_.WMB, slab_stride(), fpw_, st_);
     } else {
-      if (!gram) {
+      if (!tp.gram) {
         HTRACE("launch_period_bwd");
         launch_period_bwd(lj, G_, D.T, st_);
       }
@@ -2193,125 +2138,25 @@ class Engine {
     }
     if (md_.md.wide)   // layer-0 weight gradient from the tower's dz fragments
       launch_wgrad0(as<WideJob>(j_wide_bwd_[phase]), G_, dd(), md_.md, phase == 2, md_.WMB, nsplit_, st_);
-    enqueue_train_tail(phase);
+    enqueue_train_tail(tp);
   }
-  // k_finalize -> k_lstm_bwd -> k_wgrad as one launch (k_lstm_tail) where it applies
-  bool fused_tail_ = true;                   // DLAP_FUSED_TAIL
-  // the pipelined eval-in-forward epoch: the train split's job metrics run in the backward tail
-  // (one more block of k_lstm_tail; a launch after the tail where it is not fused) instead of on
-  // the evaluation branch, so the training chain forks only once (after the fused forward)
-  bool tail_metrics_ = false;
-  // Phase 2 (enqueue_epoch): k_finalize -> k_wgrad -> k_adam and the train metrics as ONE launch
-  // (k_lstm_tail, phase 2: the per-period sums relayed to the W_macro helpers, the moment
-  // network's clip + Adam in the last blocks), DLAP_MOM_TAIL
-  bool mom_tail_ = true;
-  bool mom_adam_ = false;                    // set around enqueue_train_grads (enqueue_epoch)
-  bool mom_tail_on(int phase) const {
-    return phase == 2 && mom_tail_ && !xs_on_ && inv_code_.p != nullptr && splits_[0].set &&
-           mom_tail_supported(md_, splits_[0].T);
-  }
-  bool mom_tail(int phase) const { return mom_adam_ && mom_tail_on(phase); }
-  // phase 2: the LSTM recurrence once per run_epochs call (DLAP_P2_LSTM_CACHE)
-  bool p2_lstm_cache_ = true;
-  bool lstm_once_ = false;
-  bool p2_lstm_cached() const {
-    return p2_lstm_cache_ && md_.nrnn > 0 && (md_.nrnn == 1 || md_.dropout == 0.f) && !xs_on_;
-  }
-  bool tail_fused(int phase) const {
-    return fused_tail_ && !xs_on_ && phase != 2 && splits_[0].set && lstm_tail_supported(md_, splits_[0].T);
-  }
-  // the pipelined eval-in-forward epoch: the clip + Adam update runs in the backward tail's last
-  // blocks (k_lstm_tail, adam 2) after the evaluation branch's bookkeeping signalled, so the
-  // training chain has no join edge and no k_adam launch (the branches join at the graph end)
-  bool tail_adam_ = true;                    // DLAP_TAIL_ADAM
-  bool tail_adam_pipe_ = false;              // DLAP_TAIL_ADAM=2: also in the one-graph fallback
-  int tail_adam_mode_ = 0;                   // set around enqueue_train_grads (enqueue_pipe)
-  float tail_lr_ = 0.f;
-  // Co-residency guard: the tail's Adam blocks spin, holding their CU slots, until the
-  // evaluation branch signals; G * nadam of them must leave at least half of the device's tail-sized
-  // slots (occupancy query, tail_cap_) to the evaluation launches they wait for, else the epoch
-  // keeps the join + k_adam update.
-  bool adam_in_tail(int phase) const {
-    if (!(tail_adam_ && tail_fused(phase) && inv_code_.p != nullptr)) return false;
-    const int nadam = (md_.P_sdf + ADAM_PB - 1) / ADAM_PB;
-    return tail_cap_ > 0 && 2 * G_ * nadam <= tail_cap_;
-  }
-  int tail_cap_ = 0;                         // k_lstm_tail workgroups resident at once (rebuild_jobs)
-  // Split epoch graphs (the pipelined eval-in-forward epoch with the update in the tail): the
-  // training chain is one single-queue graph on st_ (fused forward -> losses -> tower backward ->
-  // tail + Adam) and the evaluation branch another on st2_ (k_wait_count -> evaluation towers ->
-  // losses -> masks -> bookkeeping), launched side by side every epoch with NO graph edge between
-  // them: the evaluation graph waits in-kernel for the fused forward's evaluation recurrences
-  // (esync_ counts), the tail's Adam blocks for the bookkeeping's signal. A cross-queue edge
-  // inside a graph costs ~5-6 us on the chain and a graph that ends on two queues ~12 us at its
-  // boundary (profiles/r5_*timeline*); these cost one poll each.
-  bool split_graphs_ = true;                 // DLAP_SPLIT_GRAPHS
-  int unroll_ = 8;                           // DLAP_UNROLL: body epochs per split-graph launch
-  double host_launch_s_ = 0.0;               // host time in the pipelined body launches ...
-  long host_launch_n_ = 0;                   // ... over this many epochs (fused_info)
-  int* fwd_esig_ = nullptr;                  // set around enqueue_train_grads (enqueue_chain_split)
-  bool split_graphs(int phase) const {
-    return split_graphs_ && adam_in_tail(phase) && (sep_eval(phase) || eval_rnn_in_fwd(phase));
-  }
-  // Split epoch graphs with the evaluation recurrences on the evaluation queue (DLAP_EVAL_SEP):
-  // the training chain's fused forward runs the train recurrence only; the evaluation graph waits
-  // for the previous update (k_wait_gen) and runs its own fused LSTM + tower forward (the
-  // recurrences project their inputs, the towers trail the published periods). Bitwise equal to
-  // the default; measured slower on the bench panel (0.153 vs 0.142 ms steady,
-  // profiles/r6_eval_sep_ab.txt: the train-only fused forward still takes ~42 us, so it was not
-  // bound by the evaluation recurrences, and the evaluation graph's own fused launch contends
-  // with the chain) -- off by default.
-  bool eval_sep_ = false;
-  bool eval_sep_now_ = false;                // set around enqueue_eval_split (fused_eval)
-  bool eval_selfproj_ = false;
-  bool sep_eval(int phase) const {
-    if (!eval_sep_ || phase == 2 || n_eval_jobs_ == 0 || !fused_fwd(phase) || md_.nrnn == 0 || md_.md.wide) return false;
-    return mlp_fwd_rnn_supported(md_.md, md_.KS1, md_.WMB, md_.H, md_.nrnn, tmax_eval_) &&
-           fused_grid(eval_grid(), n_eval_jobs_, cap_eval_) > 0;
-  }
-  void enqueue_chain_split(int phase, float lr) {
-    tail_metrics_ = true;
-    const bool sep = sep_eval(phase);
-    tail_adam_mode_ = sep ? 3 : 2;
-    tail_lr_ = lr;
-    fwd_esig_ = sep ? nullptr : esync_.p;
-    enqueue_train_grads(phase, true, 0, false, !sep);
-    tail_metrics_ = false;
-    tail_adam_mode_ = 0;
-    fwd_esig_ = nullptr;
-  }
-  void enqueue_eval_split(int phase, int ignore_epoch, float sel) {      // captured on st2_
-    if (sep_eval(phase)) {
-      HTRACE("launch_wait_gen");
-      launch_wait_gen(as<UpdJob>(j_upd_), G_, prog_limit_, st2_);
-      eval_sep_now_ = true;
-      // the recurrences project their own inputs when the towers skip the moment network (cached
-      // moments); else k_proj first (gate projections + the moment bias table)
-      eval_selfproj_ = self_proj_ && h_cache_;
-      if (!eval_selfproj_) launch_proj(as<RnnJob>(j_rnn_eval_), n_eval_jobs_, tmax_eval_, dd(), md_, st2_, !h_cache_);
-      enqueue_eval_towers(st2_);
-      eval_sep_now_ = eval_selfproj_ = false;
-    } else {
-      HTRACE("launch_wait_count");
-      launch_wait_count(esync_.p, ne_per_model() * G_, prog_limit_, prog_.p, G_, st2_);
-      enqueue_eval_towers(st2_);
-    }
-    enqueue_dropmask(phase, 1, st2_);
-    enqueue_epoch_end(phase, ignore_epoch, sel, st2_, 1);
-  }
-  void enqueue_train_tail(int phase) {
+  // The backward tail: k_finalize -> k_lstm_bwd -> k_wgrad, as one launch (k_lstm_tail) where the
+  // plan says so -- then also the train metrics (tail_metrics: the pipelined eval-in-forward epoch
+  // forks only once, after the fused forward) and the update (tail_adam / mom_adam)
+  void enqueue_train_tail(const TrainPass& tp) {
+    const int phase = tp.phase;
     const SplitDev& D = splits_[0];
-    if (mom_tail(phase)) {
+    if (tp.mom_adam) {
       HTRACE("launch_lstm_tail(phase 2)");
       launch_lstm_tail(as<UpdJob>(j_upd_), as<FinJob>(j_fin_), G_, dd(), md_, D.T, slab_stride(), st_,
-                       loss_tab(2, false), 1, tail_lr_, 2);
+                       loss_tab(2, false), 1, tp.lr, 2);
       return;
     }
-    const LossJob* lm = tail_metrics_ && phase != 2 ? loss_tab(phase, use_gram(phase)) : nullptr;
-    if (tail_fused(phase)) {
+    const LossJob* lm = tp.tail_metrics && phase != 2 ? loss_tab(phase, tp.gram) : nullptr;
+    if (plan_[phase].tail_fused) {
       HTRACE("launch_lstm_tail");
       launch_lstm_tail(as<UpdJob>(j_upd_), as<FinJob>(j_fin_), G_, dd(), md_, D.T, slab_stride(), st_, lm,
-                       tail_adam_mode_, tail_lr_);
+                       tp.tail_adam, tp.lr);
       return;
     }
     if (lm) launch_job_metrics(lm, G_, st_);
@@ -2323,44 +2168,44 @@ class Engine {
     HTRACE("launch_lstm_bwd");
     launch_lstm_bwd(as<UpdJob>(j_upd_), G_, dd(), md_, D.T, phase, st_);
   }
-  hipStream_t eval_prologue_hook_ = nullptr;   // see enqueue_train_grads
-  void enqueue_train(int phase, float lr) {
-    enqueue_train_grads(phase);
+  void enqueue_update(int phase, float lr) {
     HTRACE("launch_update");
     launch_update(as<UpdJob>(j_upd_), G_, dd(), md_, phase, lr, st_, inv_code_.p != nullptr);
   }
-  void enqueue_eval(hipStream_t st) {
-    enqueue_eval_prologue(st);
-    enqueue_eval_towers(st);
+  void enqueue_train(int phase, float lr) {       // module API: dense losses, k_adam
+    enqueue_train_grads(TrainPass(phase));
+    enqueue_update(phase, lr);
   }
-  void enqueue_eval_prologue(hipStream_t st) {
+  void enqueue_eval(hipStream_t st, const EvalPass& ep) {
+    enqueue_eval_prologue(st, ep);
+    enqueue_eval_towers(st, ep);
+  }
+  void enqueue_eval_prologue(hipStream_t st, const EvalPass& ep) {
     if (n_eval_jobs_ == 0) return;
     HTRACE("launch_prologue");
     // fused: the input projections only, the recurrences run inside the tower launch
-    if (fused_eval()) launch_proj(as<RnnJob>(j_rnn_eval_), n_eval_jobs_, tmax_eval_, dd(), md_, st, !h_cache_);
-    else launch_prologue(as<RnnJob>(j_rnn_eval_), n_eval_jobs_, tmax_eval_, dd(), md_, st, !h_cache_);
+    if (fused_eval(ep)) launch_proj(as<RnnJob>(j_rnn_eval_), n_eval_jobs_, tmax_eval_, dd(), md_, st, !k_.h_cache);
+    else launch_prologue(as<RnnJob>(j_rnn_eval_), n_eval_jobs_, tmax_eval_, dd(), md_, st, !k_.h_cache);
   }
-  void enqueue_eval_towers(hipStream_t st) {
+  void enqueue_eval_towers(hipStream_t st, const EvalPass& ep) {
     if (n_eval_jobs_ == 0) return;
-    const int gx = eval_grid();
-    if (md_.md.wide && zx_eval_) {     // layer 0 streamed inside the evaluation towers
+    if (md_.md.wide && k_.zx_eval) {     // layer 0 streamed inside the evaluation towers
       HTRACE("launch_mlp_fwd_zx");
-      launch_mlp_fwd_zx(as<MlpJob>(j_mlp_eval_), n_eval_jobs_, std::max(1, zx_gx_ / n_eval_jobs_), md_.md, md_.WMB, st);
+      launch_mlp_fwd_zx(as<MlpJob>(j_mlp_eval_), n_eval_jobs_, std::max(1, k_.zx_gx / n_eval_jobs_), md_.md, md_.WMB, st);
     } else {
       if (md_.md.wide)
         launch_proj0(as<WideJob>(j_wide_eval_), n_eval_jobs_, std::max(gx_proj_[1], gx_proj_[2]), md_.md, md_.WMB, st);
       HTRACE("launch_mlp_fwd");
-      if (fused_eval())
-        launch_mlp_fwd_rnn(as<MlpJob>(j_mlp_eval_), as<RnnJob>(j_rnn_eval_), dd(), n_eval_jobs_, fused_eval_gx(),
-                           md_.md, md_.KS1, md_.WMB, md_.H, md_.nrnn, tmax_eval_, st, h_cache_, 0, eval_selfproj_);
+      if (fused_eval(ep))
+        launch_mlp_fwd_rnn(as<MlpJob>(j_mlp_eval_), as<RnnJob>(j_rnn_eval_), dd(), n_eval_jobs_, plan_[1].eval_gx_solo,
+                           md_.md, md_.KS1, md_.WMB, md_.H, md_.nrnn, tmax_eval_, st, k_.h_cache, 0, ep.selfproj);
       else
-        launch_mlp_fwd(as<MlpJob>(j_mlp_eval_), n_eval_jobs_, gx, md_.md, md_.KS1, md_.WMB, st, h_cache_);
+        launch_mlp_fwd(as<MlpJob>(j_mlp_eval_), n_eval_jobs_, eval_grid(), md_.md, md_.KS1, md_.WMB, st, k_.h_cache);
     }
-    const bool eg = eval_gram_now();
-    const LossJob* le = as<LossJob>(eg ? j_loss_eval_ : j_loss_eval_dense_);
+    const LossJob* le = as<LossJob>(ep.gram ? j_loss_eval_ : j_loss_eval_dense_);
     HTRACE("launch_period_fwd");
     period_fwd(le, n_eval_jobs_, tmax_eval_, st, false, 6);
-    if (eg) {                        // quadratic-form terms per period (no asset passes)
+    if (ep.gram) {                   // quadratic-form terms per period (no asset passes)
       HTRACE("launch_period_bwd(eval)");
       launch_period_bwd(le, n_eval_jobs_, tmax_eval_, st);
     } else {
@@ -2371,95 +2216,120 @@ class Engine {
     HTRACE("launch_job_metrics");
     launch_job_metrics(le, n_eval_jobs_, st);
   }
+  // the evaluation running alone on the GPU (the sequential epoch, the pipeline's tail)
+  void enqueue_eval_solo(int phase) {
+    EvalPass ep = eval_pass(phase);
+    ep.solo = true;
+    enqueue_eval(st_, ep);
+  }
   void enqueue_epoch_end(int phase, int ignore_epoch, float sel, hipStream_t st, int signal = 0) {
     HTRACE("launch_epoch_end");
     launch_epoch_end(as<EpochJob>(j_epoch_[phase]), G_, phase, ignore_epoch, sel, md_.residual_factor,
                      md_.P, st, signal);
   }
   // sequential epoch: train step, evaluation, bookkeeping
-  void enqueue_epoch(int phase, float lr, int ignore_epoch, float sel) {
-    const bool mt = mom_tail_on(phase);
-    mom_adam_ = mt;
-    tail_lr_ = lr;
-    enqueue_train_grads(phase);
-    mom_adam_ = false;
-    if (!mt) {
-      HTRACE("launch_update");
-      launch_update(as<UpdJob>(j_upd_), G_, dd(), md_, phase, lr, st_, inv_code_.p != nullptr);
-    }
-    if (phase != 2) { SoloScope solo(eval_solo_); enqueue_eval(st_); }
+  void enqueue_epoch(int phase, float lr, int ignore_epoch, float sel, bool lstm_once) {
+    TrainPass tp = epoch_pass(phase, lr);
+    tp.mom_adam = plan_[phase].mom_tail;
+    tp.lstm_once = lstm_once;
+    enqueue_train_grads(tp);
+    if (!tp.mom_adam) enqueue_update(phase, lr);
+    if (phase != 2) enqueue_eval_solo(phase);
     enqueue_epoch_end(phase, ignore_epoch, sel, st_);
   }
-  void enqueue_head(int phase, float lr) {
-    enqueue_train_grads(phase);
+  // the head epoch of a pipelined run trains only (part: see TrainPass, launch_head)
+  void enqueue_head(int phase, float lr, int part) {
+    TrainPass tp = epoch_pass(phase, lr);
+    tp.part = part;
+    enqueue_train_grads(tp);
     enqueue_dropmask(phase, 1, st_);                     // masks of the first pipelined epoch
-    HTRACE("launch_update");
-    launch_update(as<UpdJob>(j_upd_), G_, dd(), md_, phase, lr, st_, inv_code_.p != nullptr);
+    enqueue_update(phase, lr);
     // (k_adam does not count as a tail update: the first evaluation graph's wait passes)
-    if (split_graphs(phase) && sep_eval(phase)) launch_gen_sync(as<UpdJob>(j_upd_), G_, st_);
+    if (plan_[phase].split_graphs && plan_[phase].sep_eval) launch_gen_sync(as<UpdJob>(j_upd_), G_, st_);
+  }
+  // Split epoch graphs, the training chain (st_): the train metrics and the update run in the tail
+  void enqueue_chain_split(int phase, float lr) {
+    const bool sep = plan_[phase].sep_eval;
+    TrainPass tp = epoch_pass(phase, lr);
+    tp.premasked = true;
+    tp.tail_metrics = true;
+    tp.tail_adam = sep ? 3 : 2;
+    tp.eval_rnn = !sep;
+    tp.esig = sep ? nullptr : esync_.p;
+    enqueue_train_grads(tp);
+  }
+  // ... and the evaluation graph (captured on st2_)
+  void enqueue_eval_split(int phase, int ignore_epoch, float sel) {
+    EvalPass ep = eval_pass(phase);
+    if (plan_[phase].sep_eval) {
+      HTRACE("launch_wait_gen");
+      launch_wait_gen(as<UpdJob>(j_upd_), G_, k_.spin_limit, st2_);
+      ep.sep = true;
+      // the recurrences project their own inputs when the towers skip the moment network (cached
+      // moments); else k_proj first (gate projections + the moment bias table)
+      ep.selfproj = k_.self_proj && k_.h_cache;
+      if (!ep.selfproj) launch_proj(as<RnnJob>(j_rnn_eval_), n_eval_jobs_, tmax_eval_, dd(), md_, st2_, !k_.h_cache);
+    } else {
+      HTRACE("launch_wait_count");
+      launch_wait_count(esync_.p, ne_per_model() * G_, k_.spin_limit, prog_.p, G_, st2_);
+    }
+    enqueue_eval_towers(st2_, ep);
+    enqueue_dropmask(phase, 1, st2_);
+    enqueue_epoch_end(phase, ignore_epoch, sel, st2_, 1);
   }
   // One-graph pipelined epoch (the split graphs' fallback: DLAP_SPLIT_GRAPHS=0, the update outside
   // the tail, or no fused forward): the training chain on st_, the evaluation branch forked
   // onto st2_ and joined before the update.
   void enqueue_pipe(int phase, float lr, int ignore_epoch, float sel) {
-    HIP_OK(hipEventRecord(ev_fork_, st_));
-    HIP_OK(hipStreamWaitEvent(st2_, ev_fork_, 0));
-    if (eval_rnn_in_fwd(phase)) {
+    HIP_OK(hipEventRecord(ev_[EV_FORK], st_));
+    HIP_OK(hipStreamWaitEvent(st2_, ev_[EV_FORK], 0));
+    TrainPass tp = epoch_pass(phase, lr);
+    tp.premasked = true;
+    const EvalPass ep = eval_pass(phase);
+    if (plan_[phase].eval_in_fwd) {
       // the evaluation recurrences run inside this epoch's fused training forward; the
       // evaluation branch forks after it: towers, losses, the bookkeeping and the next epoch's
       // dropout masks, beside the training backward and its tail (which computes the train
-      // split's metrics)
-      // (the one-graph fallback keeps the join + k_adam update unless DLAP_TAIL_ADAM=2: an
-      // in-kernel wait across the graph's two branches would rest on the runtime mapping them
-      // to different hardware queues -- ADVICE r5)
-      const bool ta = tail_adam_pipe_ && adam_in_tail(phase);
-      tail_metrics_ = true;
-      tail_adam_mode_ = ta ? 2 : 0;
-      tail_lr_ = lr;
-      enqueue_train_grads(phase, true, 2, false, true);
-      tail_metrics_ = false;
-      tail_adam_mode_ = 0;
-      HIP_OK(hipStreamWaitEvent(st2_, ev_a_, 0));
-      enqueue_eval_towers(st2_);
+      // split's metrics, and the update too where run_mode says so)
+      const bool ta = run_mode(phase).tail_adam;
+      tp.eval_rnn = tp.mark_fwd = tp.tail_metrics = true;
+      tp.tail_adam = ta ? 2 : 0;
+      enqueue_train_grads(tp);
+      HIP_OK(hipStreamWaitEvent(st2_, ev_[EV_FWD], 0));
+      enqueue_eval_towers(st2_, ep);
       if (ta) {
         // the next epoch's masks, then the bookkeeping, whose signal releases the tail's update
         // (both read counters / parameters the update writes)
         enqueue_dropmask(phase, 1, st2_);
         enqueue_epoch_end(phase, ignore_epoch, sel, st2_, 1);
-        HIP_OK(hipEventRecord(ev_join_, st2_));
-        HIP_OK(hipStreamWaitEvent(st_, ev_join_, 0));
+        HIP_OK(hipEventRecord(ev_[EV_JOIN], st2_));
+        HIP_OK(hipStreamWaitEvent(st_, ev_[EV_JOIN], 0));
         return;
       }
       enqueue_epoch_end(phase, ignore_epoch, sel, st2_);
       enqueue_dropmask(phase, 1, st2_);
     } else {
       // training-chain nodes first (they land on the graph's first queue); the evaluation
-      // branch's LSTM prologue right behind the training one (eval_prologue_hook_), so its
+      // branch's LSTM prologue right behind the training one (TrainPass::eval_prologue), so its
       // serial recurrence starts at the epoch start; this epoch's train metrics on the
-      // evaluation branch after the loss pass (ev_mid_), then the bookkeeping and the masks
-      eval_prologue_hook_ = st2_;
-      enqueue_train_grads(phase, true, 0, true);
-      eval_prologue_hook_ = nullptr;
-      enqueue_eval_towers(st2_);
+      // evaluation branch after the loss pass (EV_MID), then the bookkeeping and the masks
+      tp.eval_prologue = st2_;
+      tp.defer_metrics = true;
+      enqueue_train_grads(tp);
+      enqueue_eval_towers(st2_, ep);
       if (phase != 2) {
-        HIP_OK(hipStreamWaitEvent(st2_, ev_mid_, 0));
-        launch_job_metrics(loss_tab(phase, use_gram(phase)), G_, st2_);
+        HIP_OK(hipStreamWaitEvent(st2_, ev_[EV_MID], 0));
+        launch_job_metrics(loss_tab(phase, tp.gram), G_, st2_);
       }
       enqueue_epoch_end(phase, ignore_epoch, sel, st2_);
       enqueue_dropmask(phase, 1, st2_);
     }
-    HIP_OK(hipEventRecord(ev_join_, st2_));
-    HIP_OK(hipStreamWaitEvent(st_, ev_join_, 0));
-    HTRACE("launch_update");
-    launch_update(as<UpdJob>(j_upd_), G_, dd(), md_, phase, lr, st_, inv_code_.p != nullptr);
+    HIP_OK(hipEventRecord(ev_[EV_JOIN], st2_));
+    HIP_OK(hipStreamWaitEvent(st_, ev_[EV_JOIN], 0));
+    enqueue_update(phase, lr);
   }
-  struct SoloScope {
-    bool& f;
-    explicit SoloScope(bool& x) : f(x) { f = true; }
-    ~SoloScope() { f = false; }
-  };
   void enqueue_tail(int phase, int ignore_epoch, float sel) {
-    { SoloScope solo(eval_solo_); enqueue_eval(st_); }
+    enqueue_eval_solo(phase);
     enqueue_epoch_end(phase, ignore_epoch, sel, st_);
   }
   template <typename F>
@@ -2473,7 +2343,16 @@ class Engine {
       std::lock_guard<std::mutex> g(g_legacy_mu);
       HTRACE("capture %s tid=%ld", key.c_str(), (long)syscall(SYS_gettid));
       HIP_OK(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
-      enqueue();
+      try {
+        enqueue();
+      } catch (...) {
+        // do not leave the stream capturing: end the capture, drop what it recorded, rethrow
+        hipGraph_t partial = nullptr;
+        (void)hipStreamEndCapture(cs, &partial);
+        if (partial) (void)hipGraphDestroy(partial);
+        (void)hipGetLastError();
+        throw;
+      }
       HTRACE("end capture");
       HIP_OK(hipStreamEndCapture(cs, &graph));
     }
@@ -2516,10 +2395,10 @@ class Engine {
     DevBuf<char>& b = F.m;
     DevBuf<char>& c = F.l;
     DevBuf<char>& w = F.w;
-    const bool zx = md_.md.wide && zx_eval_ && !train_mode;
+    const bool zx = md_.md.wide && k_.zx_eval && !train_mode;
     if (md_.md.wide && !zx) launch_proj0(as<WideJob>(w), G_, gx_proj_[s], md_.md, md_.WMB, st_);
     launch_prologue(as<RnnJob>(a), G_, D.T, dd(), md_, st_, do_mom);
-    if (zx) launch_mlp_fwd_zx(as<MlpJob>(b), G_, std::max(1, zx_gx_ / G_), md_.md, md_.WMB, st_);
+    if (zx) launch_mlp_fwd_zx(as<MlpJob>(b), G_, std::max(1, k_.zx_gx / G_), md_.md, md_.WMB, st_);
     else launch_mlp_fwd(as<MlpJob>(b), G_, gx_fwd_[s], md_.md, md_.KS1, md_.WMB, st_);
     period_fwd(as<LossJob>(c), G_, D.T, st_, true, 1 << s);
     launch_asset(as<LossJob>(c), G_, D.N, md_.K, st_);

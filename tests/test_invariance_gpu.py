@@ -476,3 +476,45 @@ def test_concurrent_engines_split_graphs_no_giveups(big):
         out = (eng.params(0), np.nan_to_num(eng.history_rows(0), nan=-7.0), eng.params(0, "sharpe"),
                eng.params(0, "loss"))
         _same(ref[s], out)
+
+
+def test_safe_mode_round_trip_restores_the_launch_plan():
+    """An engine that has trained, switched to safe mode and back: its launch plan (fused_info,
+    but for the host launch timing) is a fresh engine's, and further epochs of every phase give
+    the bits of an engine that was never switched."""
+    from deeplearninginassetpricing_paperreplication_amd.data.synthetic import generate_panel_fast
+    from deeplearninginassetpricing_paperreplication_amd.engine.runner import GANEngine
+    ret, feats, mask, mac = generate_panel_fast(96, 600, 46, 8, seed=1)
+    mac = (mac - mac.mean(0)) / (mac.std(0, unbiased=False) + 1e-8)
+    b = {"returns": ret, "individual_features": feats, "mask": mask, "macro_features": mac}
+    cfg = default_cli_config(8, 46)
+
+    def make(epochs):
+        torch.manual_seed(0)
+        eng = GANEngine(AssetPricingGAN(cfg).spec, 1, max_epochs=32)
+        eng.set_data(b, b, b)
+        eng.set_model(0, AssetPricingGAN(cfg), 3)
+        if epochs:
+            eng.eng.begin_phase(1)
+            eng.run(1, epochs, 1e-3, 0, 1.0, True)
+        return eng
+
+    def plan(eng):
+        return {k: v for k, v in eng.eng.fused_info().items() if k != "host_launch_us_per_epoch"}
+
+    ref, eng, fresh = make(4), make(4), make(0)
+    eng.eng.set_safe_mode(True)
+    assert plan(eng) != plan(fresh)          # (safe mode does change the plan: no fused forward)
+    eng.eng.set_safe_mode(False)
+    assert plan(eng) == plan(fresh)
+    out = []
+    for e in (ref, eng):
+        e.run(1, 5, 1e-3, 0, 1.0, True)
+        for ph, n in ((2, 2), (3, 4)):
+            e.eng.begin_phase(ph)
+            e.run(ph, n, 1e-3, 0, 1.0, True)
+        e.eng.sync()
+        assert e.eng.prog_timeouts() == 0
+        out.append((e.params(0), np.nan_to_num(e.history_rows(0), nan=-7.0), e.params(0, "sharpe"),
+                    e.params(0, "loss")))
+    _same(*out)
