@@ -38,6 +38,7 @@
 #include "engine_plan.h"
 #include "layout.h"
 #include "loss.h"
+#include "macro_sens.h"
 #include "mlp.h"
 #include "panel.h"
 #include "rnn.h"
@@ -788,6 +789,93 @@ class Engine {
     for (int c = 0; c < C; ++c) e.mutable_at(c) = host[(size_t)(2 * G_) * C + c];
     py::dict d;
     d["abs"] = a; d["sum"] = b; d["ens"] = e; d["rows"] = D.R;
+    return d;
+  }
+  // Macro importance of split s through the LSTM (k_macro_sens.hip): the gradient of the raw SDF
+  // weight with respect to the standardised macro series fed l periods before the row's period,
+  // for the lags l = 0 .. L - 1 (L = lags clamped to T) and for their sum, reduced over the split's
+  // rows. `scale` / `refresh` as for input_sensitivity. The split's recurrence is run once more in
+  // evaluation mode with save buffers of this call (the outputs are the same values: k_rnn.hip
+  // stores the saved copies beside them); everything allocated here is released on return.
+  // Returns fp64 abs [G][L][M] = sum_rows |dw_g/dm[t-l]|, ens [L][M] = sum_rows |sum_g ...|,
+  // cum [M] = sum_rows |sum_g sum_l ...|, rows (= R) and gpu_ms (prologue, k_lstm_lagjac,
+  // k_macro_sens + reduce).
+  bool macro_sens_ok() const { return macro_sens_supported(md_.md, md_.KS1, md_.nrnn, md_.H, G_); }
+  py::dict macro_sensitivity(int s, uintptr_t scale, int lags, bool refresh = true) {
+    if (s < 0 || s > 2) throw std::invalid_argument("split must be 0, 1 or 2");
+    if (lags < 1) throw std::invalid_argument("macro_sensitivity: lags must be >= 1");
+    ensure_jobs();
+    const SplitDev& D = splits_[s];
+    if (!D.set) throw std::runtime_error("split not set");
+    if (md_.nrnn == 0) throw std::invalid_argument("macro_sensitivity: the model has no LSTM (the state columns are the macro series)");
+    if (md_.nrnn != 1 || md_.H > 8)
+      throw std::invalid_argument("macro_sensitivity: not available for stacked LSTMs or more than 8 units");
+    if (!macro_sens_ok())
+      throw std::invalid_argument("macro_sensitivity: not available for this shape (wide layer-0 path, or the "
+                                  "fragments and state gradients exceed the LDS budget)");
+    MacroDims A{};
+    A.G = G_; A.T = D.T; A.R = D.R; A.L = std::min(lags, std::max(D.T, 1)); A.M = md_.M; A.H = md_.H;
+    A.w_ih = md_.lstm_w_ih[0]; A.w_hh = md_.lstm_w_hh[0];
+    const int L = A.L, M = A.M, nrows = G_ * L + L + 1;
+    std::vector<double> host(macro_out_doubles(A), 0.0);
+    float ms[3] = {0.f, 0.f, 0.f};
+    if (D.R > 0) {
+      if (refresh) fwd_only(s, false, false, false);
+      DevBuf<char> tj, tsj, trj, tlj;
+      DevBuf<float> scl, part, C, sg, sc, sh;
+      DevBuf<double> res;
+      const size_t ns = (size_t)G_ * D.T, H = md_.H;
+      scl.alloc(ns, false);
+      if (scale) {
+        HIP_OK(hipMemcpyAsync(scl.p, reinterpret_cast<const void*>(scale), ns * sizeof(float),
+                              hipMemcpyDeviceToDevice, st_));
+      } else {
+        sync();
+        const std::vector<float> ones(ns, 1.f);
+        HIP_LEGACY(hipMemcpy(scl.p, ones.data(), ns * sizeof(float), hipMemcpyHostToDevice));
+      }
+      sg.alloc(ns * 4 * H); sc.alloc(ns * H); sh.alloc(ns * H);
+      C.alloc(macro_c_floats(A));                    // (zero-filled: padding and t - l < 0)
+      std::vector<MlpJob> mj;
+      std::vector<SensJob> sj;
+      std::vector<RnnJob> rj;
+      std::vector<LagJob> lj;
+      for (int g = 0; g < G_; ++g) {
+        mj.push_back(mlp_job(g, s, false, true, false));
+        sj.push_back(SensJob{models_[g].params.p, scl.p + (size_t)g * D.T});
+        RnnJob r = rnn_job(g, s, false, 0);
+        r.sg = sg.p + (size_t)g * D.T * 4 * H; r.sc = sc.p + (size_t)g * D.T * H; r.sh = sh.p + (size_t)g * D.T * H;
+        rj.push_back(r);
+        lj.push_back(LagJob{models_[g].params.p, r.sg, r.sc, r.c0});
+      }
+      upload(tj, mj); upload(tsj, sj); upload(trj, rj); upload(tlj, lj);
+      part.alloc(macro_part_floats(A), false);
+      res.alloc(host.size(), false);
+      hipEvent_t ev[4];
+      for (auto& e : ev) HIP_OK(hipEventCreate(&e));
+      HIP_OK(hipEventRecord(ev[0], st_));
+      launch_prologue(as<RnnJob>(trj), G_, D.T, dd(), md_, st_, false, true);
+      HIP_OK(hipEventRecord(ev[1], st_));
+      launch_lstm_lagjac(as<LagJob>(tlj), A, C.p, st_);
+      HIP_OK(hipEventRecord(ev[2], st_));
+      launch_macro_sens(as<MlpJob>(tj), as<SensJob>(tsj), A, md_.md, md_.KS1, md_.s[0], C.p, part.p, res.p, st_);
+      HIP_OK(hipEventRecord(ev[3], st_));
+      sync();
+      for (int i = 0; i < 3; ++i) HIP_OK(hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]));
+      for (auto& e : ev) HIP_OK(hipEventDestroy(e));
+      HIP_LEGACY(hipMemcpy(host.data(), res.p, host.size() * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    (void)nrows;
+    py::array_t<double> a({G_, L, M}), e({L, M}), c({M});
+    for (int g = 0; g < G_; ++g)
+      for (int l = 0; l < L; ++l)
+        for (int j = 0; j < M; ++j) a.mutable_at(g, l, j) = host[((size_t)g * L + l) * M + j];
+    for (int l = 0; l < L; ++l)
+      for (int j = 0; j < M; ++j) e.mutable_at(l, j) = host[((size_t)G_ * L + l) * M + j];
+    for (int j = 0; j < M; ++j) c.mutable_at(j) = host[((size_t)G_ * L + L) * M + j];
+    py::dict d;
+    d["abs"] = a; d["ens"] = e; d["cum"] = c; d["rows"] = D.R;
+    d["gpu_ms"] = py::make_tuple(ms[0], ms[1], ms[2]);
     return d;
   }
   void train_step(int phase, float lr) {
@@ -2502,6 +2590,9 @@ PYBIND11_MODULE(_dlap_hip, m) {
       .def("input_sensitivity", &Engine::input_sensitivity, py::arg("s"), py::arg("scale") = 0,
            py::arg("refresh") = true)
       .def("sens_supported", [](Engine& e) { return e.sens_ok(); })
+      .def("macro_sensitivity", &Engine::macro_sensitivity, py::arg("s"), py::arg("scale") = 0, py::arg("lags") = 1,
+           py::arg("refresh") = true)
+      .def("macro_sens_supported", [](Engine& e) { return e.macro_sens_ok(); })
       .def("train_step", &Engine::train_step)
       .def("backward_only", &Engine::backward_only, py::arg("phase"), py::arg("wait") = true)
       .def("set_stream", &Engine::set_stream, py::arg("stream"), py::arg("external") = true)

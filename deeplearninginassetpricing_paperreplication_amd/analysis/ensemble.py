@@ -87,12 +87,15 @@ def weights_batched_gpu(models: Sequence, batches: Dict[str, Dict]) -> Dict[str,
 
 def evaluate_ensemble(checkpoint_dirs: Sequence[str], data_dir: str, device: str = "cpu",
                       verbose: bool = True, paper: bool = False, importance: bool = False,
-                      importance_split: str = "test", importance_out: str = None) -> Dict:
+                      importance_split: str = "test", importance_out: str = None,
+                      importance_macro_lags: int = 0) -> Dict:
     """Reference output and return value; ``paper=True`` (CLI ``--paper_metrics``) adds the
     paper's EV / XS-R² / turnover / max 1-month loss of the ensemble's SDF factor per split;
     ``importance=True`` (CLI ``--variable_importance``) adds the sensitivity ranking of the
     ensemble weight on ``importance_split`` (``analysis.importance``) under the key
-    ``variable_importance`` and writes it to ``importance_out`` (JSON) when given."""
+    ``variable_importance`` and writes it to ``importance_out`` (JSON) when given;
+    ``importance_macro_lags = L > 0`` (CLI ``--importance_macro_lags``) adds the importance of
+    the macro series through the LSTM for the lags 0 .. L-1 to that ranking."""
     say = print if verbose else (lambda *a, **k: None)
     bar = "=" * 70
     say(bar); say(f"ENSEMBLE EVALUATION ({len(checkpoint_dirs)} models, averaged weights)"); say(bar); say()
@@ -152,8 +155,11 @@ def evaluate_ensemble(checkpoint_dirs: Sequence[str], data_dir: str, device: str
         if importance_split not in SPLITS:
             raise ValueError(f"importance_split must be one of {SPLITS}")
         ds = datasets[SPLITS.index(importance_split)]
+        kw = {}
+        if importance_macro_lags:
+            kw = dict(macro_lags=int(importance_macro_lags), macro_names=getattr(ds, "macro_names", None))
         imp = variable_importance(models, batches[importance_split], device=device,
-                                  names=getattr(ds, "variable_names", None))
+                                  names=getattr(ds, "variable_names", None), **kw)
         out["variable_importance"] = imp
         say(bar); say(f"VARIABLE IMPORTANCE ({importance_split} split, ensemble weight)"); say(bar); say()
         for line in format_importance(imp):
@@ -176,10 +182,13 @@ def main(argv=None):
                    help="also print the sensitivity ranking of the ensemble weight")
     p.add_argument("--importance_split", type=str, default="test", choices=SPLITS)
     p.add_argument("--importance_out", type=str, default=None, help="write the ranking to FILE.json")
+    p.add_argument("--importance_macro_lags", type=int, default=0,
+                   help="with --variable_importance: also rank the macro series through the LSTM, lags 0..L-1")
     a = p.parse_args(argv)
+    kw = {"importance_macro_lags": a.importance_macro_lags} if a.importance_macro_lags else {}
     return evaluate_ensemble(a.checkpoint_dirs, a.data_dir, a.device, paper=a.paper_metrics,
                              importance=a.variable_importance, importance_split=a.importance_split,
-                             importance_out=a.importance_out)
+                             importance_out=a.importance_out, **kw)
 
 
 if __name__ == "__main__":

@@ -21,8 +21,32 @@ Two scales of model g's output in period t:
 for all models of the ensemble; mixed-architecture ensembles and shapes the kernel does not cover
 (the wide layer-0 path) fall back to the CPU path with a printed note.
 
-Out of scope: the importance of the raw macro series THROUGH the LSTM (a per-row BPTT), per-period
-breakdowns, and the moment network.
+Macro importance through the LSTM (``macro_lags = L > 0``). ``m`` is the standardised macro series
+the model is fed (``batch["macro_features"]``), ``w`` the ensemble weight with the same ``scale``
+semantics (members summed with their signs per row before the absolute value). The split's
+recurrence starts from the engine's ``h0 / c0`` (zero unless set), and macro values before the
+split's first period are constants. For the lags ``l = 0 .. L-1`` (``L`` clamped to ``T``):
+
+    macro_lag[l][j] = (1 / rows_lag[l]) * sum over valid rows (t,i), t >= l, of
+                          | sum_g s_g,t * d w_g(t,i) / d m[t-l][j] |
+    macro_cum[j]    = (1 / rows) * sum over valid rows of
+                          | sum_{l < min(L, t+1)} sum_g s_g,t * d w_g(t,i) / d m[t-l][j] |
+
+``rows_lag[l]`` is the number of valid rows in the periods ``t >= l``; ``macro`` is ``macro_lag[0]``
+normalised to sum to one (the current-month ranking of the paper's macro figure) and ``macro_cum``
+the response to a shift of series ``j`` sustained over the window. The dependence on the macro
+history factors through the state columns,
+
+    d w_g(t,i) / d m[t-l][j] = sum_k d_g(t,i)[k] * J_g[t][l][k][j],   J_g[t][l] = d h_t / d m_{t-l},
+
+so it is a per-period Jacobian times the per-row state gradient, not a per-row BPTT. The CPU path
+takes ``J`` from autograd of ``macro_lstm`` (any depth); the engine (``csrc/k_macro_sens.hip``)
+covers single-layer LSTMs of up to 8 units on the fused layer-0 path and everything else falls
+back to the CPU path. Without an LSTM the state columns are the macro series: ``macro_lag[0]`` is
+the state-column result and the higher lags are zero.
+
+Out of scope: per-period breakdowns, the moment network, and the indirect effect through the
+weight normalisation.
 """
 from __future__ import annotations
 
@@ -102,7 +126,69 @@ def _cpu_sums(models, batch, scale: str, dtype, chunk: int = 16) -> Dict:
     return {"abs": ab, "sum": sm, "ens": ens, "rows": int(mask.sum()), "F": F, "Dm": Dm}
 
 
-def _gpu_sums(models, batch, scale: str) -> Optional[Dict]:
+def _lag_jacobians(lstm, macro, L: int):
+    """J [T, L, H, M] = d h_t / d m_{t-l} of ``macro_lstm`` (zero where t - l < 0): per period the
+    H unit seeds are carried back by autograd (batched where the LSTM backward supports it)."""
+    m = macro.detach().clone().requires_grad_(True)
+    h = lstm(m)[0]
+    T, H = h.shape
+    J = torch.zeros(T, L, H, m.shape[1], dtype=macro.dtype)
+    eye = torch.eye(H, dtype=h.dtype)
+    batched = True
+    for t in range(T):
+        g = None
+        if batched:
+            try:
+                g = torch.autograd.grad(h[t], m, grad_outputs=eye, is_grads_batched=True, retain_graph=True)[0]
+            except RuntimeError:
+                batched = False
+        if g is None:
+            g = torch.stack([torch.autograd.grad(h[t, k], m, retain_graph=True)[0] for k in range(H)])
+        n = min(L, t + 1)
+        J[t, :n] = g[:, t - n + 1:t + 1].flip(1).permute(1, 0, 2)      # lag l is period t - l
+    return J
+
+
+def _cpu_macro(models, batch, scale: str, dtype, lags: int) -> Dict:
+    """m_abs [G, L, M], m_ens [L, M], m_cum [M] (float64): the per-row state gradients contracted
+    with the per-period lag Jacobians of every model's LSTM, in period chunks."""
+    feats = batch["individual_features"].to(dtype)
+    mask = batch["mask"].bool()
+    macro = batch["macro_features"].to(dtype)
+    T, N, F = feats.shape
+    M = int(macro.shape[1])
+    G, Lg = len(models), min(int(lags), T)
+    ms = [copy.deepcopy(m).to(dtype).eval() for m in models]
+    if not all(_has_lstm(m) for m in ms):
+        raise ValueError("variable_importance: macro lags need an LSTM in every model")
+    states = [_state(m, macro) for m in ms]
+    if len({int(s.shape[-1]) for s in states}) != 1:
+        raise ValueError("variable_importance: the models' state widths differ")
+    Dm = int(states[0].shape[-1])
+    jac = [_lag_jacobians(m.sdf_net.macro_lstm, macro, Lg).double() for m in ms]
+    ab = np.zeros((G, Lg, M)); ens = np.zeros((Lg, M)); cum = np.zeros(M)
+    chunk = max(1, min(16, int(4e6 // max(N * Lg * M, 1))))
+    for t0 in range(0, T, chunk):
+        t1 = min(T, t0 + chunk)
+        mk = mask[t0:t1]
+        tot = torch.zeros(Lg, t1 - t0, N, M, dtype=torch.float64)
+        for g, m in enumerate(ms):
+            st = states[g][t0:t1, None, :].expand(t1 - t0, N, Dm).clone().requires_grad_(True)
+            net = m.sdf_net
+            w_raw = net.output_proj(net.fc_layers(torch.cat([feats[t0:t1], st], -1).reshape(-1, F + Dm)))
+            w_raw = w_raw.reshape(t1 - t0, N)
+            ds = torch.autograd.grad(w_raw.sum(), st)[0]
+            s = _model_scale(w_raw.detach(), mk, net.normalize_weights, G, scale)
+            d = ds.double() * s.double()[:, None, None] * mk[:, :, None].double()
+            p = torch.einsum("tik,tlkj->ltij", d, jac[g][t0:t1])
+            ab[g] += p.abs().sum((1, 2)).numpy()
+            tot += p
+        ens += tot.abs().sum((1, 2)).numpy()
+        cum += tot.sum(0).abs().sum((0, 1)).numpy()
+    return {"m_abs": ab, "m_ens": ens, "m_cum": cum}
+
+
+def _gpu_sums(models, batch, scale: str, macro_lags: int = 0) -> Optional[Dict]:
     """The same sums from the native engine, or None (with a printed note) where it does not apply."""
     specs = {m.spec for m in models}
     if len(specs) != 1:
@@ -133,16 +219,22 @@ def _gpu_sums(models, batch, scale: str) -> Optional[Dict]:
             sc = (1.0 / (G * wn.abs().sum(dim=2).clamp(min=1e-8))).contiguous()
             refresh = False
         torch.cuda.synchronize(dev)
+        mr = None
         try:
             r = e.input_sensitivity(0, sc.data_ptr(), refresh)
+            if macro_lags > 0 and _has_lstm(models[0]):      # (the forward above left the state current)
+                mr = e.macro_sensitivity(0, sc.data_ptr(), int(macro_lags), False)
         except ValueError as err:
             print(f"[importance] {err}: using the CPU path")
             return None
     finally:
         e.sync()
     F = spec.individual_dim
-    return {"abs": np.asarray(r["abs"]), "sum": np.asarray(r["sum"]), "ens": np.asarray(r["ens"]),
-            "rows": int(r["rows"]), "F": F, "Dm": int(np.asarray(r["ens"]).shape[0]) - F}
+    out = {"abs": np.asarray(r["abs"]), "sum": np.asarray(r["sum"]), "ens": np.asarray(r["ens"]),
+           "rows": int(r["rows"]), "F": F, "Dm": int(np.asarray(r["ens"]).shape[0]) - F}
+    if mr is not None:
+        out.update(m_abs=np.asarray(mr["abs"]), m_ens=np.asarray(mr["ens"]), m_cum=np.asarray(mr["cum"]))
+    return out
 
 
 def _unit(v: np.ndarray) -> np.ndarray:
@@ -150,8 +242,33 @@ def _unit(v: np.ndarray) -> np.ndarray:
     return v / s if s > 0 else v
 
 
+def _macro_result(r: Dict, mask, lags: int, lstm: bool, G: int, macro_names: Optional[Sequence]) -> Dict:
+    """The macro keys of the result from the raw sums (m_* with an LSTM, else the state columns)."""
+    per = mask.bool().sum(1).cpu().numpy().astype(np.int64)
+    T = int(per.shape[0])
+    Lg = min(int(lags), T)
+    rows_lag = np.array([int(per[l:].sum()) for l in range(Lg)], dtype=np.int64)
+    den = np.maximum(rows_lag, 1).astype(np.float64)
+    rows = max(int(r["rows"]), 1)
+    if lstm:
+        m_abs, m_ens, m_cum = r["m_abs"], r["m_ens"], r["m_cum"]
+    else:                                   # the state columns are the macro series themselves
+        F, Dm = r["F"], r["Dm"]
+        m_abs = np.zeros((G, Lg, Dm)); m_ens = np.zeros((Lg, Dm))
+        m_abs[:, 0] = r["abs"][:, F:]
+        m_ens[0] = r["ens"][F:]
+        m_cum = np.array(r["ens"][F:], dtype=np.float64)
+    M = int(m_ens.shape[1])
+    lag = m_ens / den[:, None]
+    nm = [str(n) for n in macro_names] if macro_names is not None and len(macro_names) == M \
+        else [f"macro{j}" for j in range(M)]
+    return {"macro": _unit(lag[0]), "macro_lag": lag, "macro_cum": m_cum / rows,
+            "per_model_macro_lag": m_abs / den[None, :, None], "rows_lag": rows_lag, "macro_names": nm}
+
+
 def variable_importance(models: Sequence, batch: Dict, device: str = "cpu", scale: str = "ensemble",
-                        dtype: torch.dtype = torch.float32, names: Optional[Sequence] = None) -> Dict:
+                        dtype: torch.dtype = torch.float32, names: Optional[Sequence] = None,
+                        macro_lags: int = 0, macro_names: Optional[Sequence] = None) -> Dict:
     """Sensitivity of the ensemble SDF weight to every tower input column over ``batch``.
 
     Returns ``characteristics`` [F] and ``state`` [Dm] (mean absolute gradient of the ensemble
@@ -162,25 +279,40 @@ def variable_importance(models: Sequence, batch: Dict, device: str = "cpu", scal
     ``scale="ensemble"`` is the direct-effect gradient of the averaged L1-normalised weight: each
     model's per-period mean and L1 norm are held constant (see the module docstring).
     ``dtype`` applies to the CPU path; the engine computes in its own precision.
+
+    ``macro_lags = L > 0`` adds the importance of the macro series through the LSTM (module
+    docstring): ``macro`` [M], ``macro_lag`` [L][M], ``macro_cum`` [M], ``per_model_macro_lag``
+    [G][L][M], ``rows_lag`` [L] and ``macro_names`` (``macro_names`` when given, else macro0..);
+    ``L`` is clamped to the number of periods. ``0`` leaves the result as it is without it.
     """
     if scale not in ("ensemble", "raw"):
         raise ValueError("scale must be 'ensemble' or 'raw'")
+    if int(macro_lags) < 0:
+        raise ValueError("macro_lags must be >= 0")
+    macro_lags = int(macro_lags)
     models = list(models)
     if not models:
         raise ValueError("no models")
+    lstm = _has_lstm(models[0])
     r = None
     if str(device).startswith("cuda"):
-        r = _gpu_sums(models, batch, scale)
+        r = _gpu_sums(models, batch, scale, macro_lags)
     if r is None:
         cpu = {k: (v.cpu() if isinstance(v, torch.Tensor) else v) for k, v in batch.items()}
-        r = _cpu_sums([m.cpu() if hasattr(m, "cpu") else m for m in models], cpu, scale, dtype)
+        cms = [m.cpu() if hasattr(m, "cpu") else m for m in models]
+        r = _cpu_sums(cms, cpu, scale, dtype)
+        if macro_lags > 0 and lstm:
+            r.update(_cpu_macro(cms, cpu, scale, dtype, macro_lags))
     F, Dm, rows = r["F"], r["Dm"], max(int(r["rows"]), 1)
     mean = r["ens"] / rows
-    return {
+    out = {
         "characteristics": _unit(mean[:F]), "state": _unit(mean[F:]), "abs_mean": mean,
         "per_model_abs_mean": r["abs"] / rows, "per_model_signed_mean": r["sum"] / rows,
-        "names": input_names(F, Dm, _has_lstm(models[0]), names), "rows": int(r["rows"]),
+        "names": input_names(F, Dm, lstm, names), "rows": int(r["rows"]),
     }
+    if macro_lags > 0:
+        out.update(_macro_result(r, batch["mask"], macro_lags, lstm, len(models), macro_names))
+    return out
 
 
 def format_importance(imp: Dict, top: int = 20) -> List[str]:
@@ -193,6 +325,12 @@ def format_importance(imp: Dict, top: int = 20) -> List[str]:
     if len(imp["state"]):
         lines.append("  State columns:")
         lines += [f"        {names[F + j]:<16s} {imp['state'][j]:.4f}" for j in range(len(imp["state"]))]
+    if "macro" in imp and len(imp["macro"]):
+        mo = np.argsort(-imp["macro"])[:top]
+        lines.append(f"  Top {len(mo)} macro series (share of the mean |dw/dm| at lag 0; sustained over "
+                     f"{len(imp['macro_lag'])} lag(s)):")
+        lines += [f"    {k + 1:2d}. {imp['macro_names'][j]:<16s} {imp['macro'][j]:.4f}   {imp['macro_cum'][j]:.3e}"
+                  for k, j in enumerate(mo)]
     return lines
 
 

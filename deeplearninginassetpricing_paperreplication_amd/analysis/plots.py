@@ -221,8 +221,37 @@ def plot_variable_importance(checkpoint_dirs, data_dir, save_path=None, device: 
     return fig, ax
 
 
+def plot_macro_importance(checkpoint_dirs, data_dir, save_path=None, device: str = "cpu", split: str = "test",
+                          top: int = 20, lags: int = 12, profiles: int = 5, importance: Dict = None):
+    """The ``top`` macro series by lag-0 sensitivity of the ensemble weight through the LSTM, and
+    the lag profile of the first ``profiles`` of them."""
+    if importance is None:
+        from .importance import variable_importance
+        ds = load_splits(data_dir)[SPLITS.index(split)]
+        models = [load_model(d, "cpu")[0] for d in checkpoint_dirs]
+        importance = variable_importance(models, ds.get_full_batch(), device=device, macro_lags=lags,
+                                         macro_names=getattr(ds, "macro_names", None))
+    mac, lag = np.asarray(importance["macro"]), np.asarray(importance["macro_lag"])
+    names = importance["macro_names"]
+    order = np.argsort(-mac)[:top][::-1]
+    fig, (ax, bx) = plt.subplots(1, 2, figsize=(16, 8))
+    ax.barh(np.arange(len(order)), mac[order], color="darkorange", alpha=0.8, edgecolor="black")
+    ax.set_yticks(np.arange(len(order)))
+    ax.set_yticklabels([names[j] for j in order])
+    ax.set(xlabel="Sensitivity at lag 0 (share of mean |dw/dm|)", title=f"Macro Importance (Top {len(order)}, {split})")
+    ax.grid(True, alpha=0.3, axis="x")
+    for j in np.argsort(-mac)[:profiles]:
+        bx.plot(np.arange(lag.shape[0]), lag[:, j], marker="o", label=names[j])
+    bx.set(xlabel="Lag (periods)", ylabel="Mean |dw/dm[t-l]|", title="Lag profile of the top series")
+    bx.grid(True, alpha=0.3)
+    if len(mac):
+        bx.legend()
+    _save(fig, save_path)
+    return fig, (ax, bx)
+
+
 def generate_all_plots(checkpoint_dirs, data_dir, output_dir="./plots", device: str = "cpu",
-                       variable_importance: bool = False):
+                       variable_importance: bool = False, importance_macro_lags: int = 0):
     os.makedirs(output_dir, exist_ok=True)
     print("Generating plots...")
     print("=" * 50)
@@ -241,6 +270,10 @@ def generate_all_plots(checkpoint_dirs, data_dir, output_dir="./plots", device: 
     if variable_importance:
         jobs.append(("Variable Importance", "variable_importance.png",
                      lambda p: plot_variable_importance(checkpoint_dirs, data_dir, p, device=device)))
+        if importance_macro_lags > 0:
+            jobs.append(("Macro Importance", "macro_importance.png",
+                         lambda p: plot_macro_importance(checkpoint_dirs, data_dir, p, device=device,
+                                                         lags=importance_macro_lags)))
     for i, (title, fname, fn) in enumerate(jobs, 1):
         print(f"\n{i}. {title}...")
         fn(os.path.join(output_dir, fname))
@@ -258,8 +291,13 @@ def main(argv=None):
     p.add_argument("--device", type=str, default="cpu")
     p.add_argument("--variable_importance", action="store_true",
                    help="also write variable_importance.png (top 20 characteristics)")
+    p.add_argument("--importance_macro_lags", type=int, default=0,
+                   help="with --variable_importance: also write macro_importance.png for the lags 0..L-1")
     a = p.parse_args(argv)
-    if a.variable_importance:
+    if a.variable_importance and a.importance_macro_lags > 0:
+        generate_all_plots(a.checkpoint_dirs, a.data_dir, a.output_dir, a.device, variable_importance=True,
+                           importance_macro_lags=a.importance_macro_lags)
+    elif a.variable_importance:
         generate_all_plots(a.checkpoint_dirs, a.data_dir, a.output_dir, a.device, variable_importance=True)
     else:
         generate_all_plots(a.checkpoint_dirs, a.data_dir, a.output_dir, a.device)
