@@ -41,6 +41,7 @@
 #include "macro_sens.h"
 #include "mlp.h"
 #include "panel.h"
+#include "qsort.h"
 #include "rnn.h"
 #include "update.h"
 #include "wide.h"
@@ -876,6 +877,64 @@ class Engine {
     py::dict d;
     d["abs"] = a; d["ens"] = e; d["cum"] = c; d["rows"] = D.R;
     d["gpu_ms"] = py::make_tuple(ms[0], ms[1], ms[2]);
+    return d;
+  }
+  // Characteristic-sorted portfolios of split s (k_qsort.hip, definition in qsort.h): per period and
+  // key column the Q - 1 quantile breakpoints of the valid rows' keys, and per bucket the row count
+  // and the fp64 sums of the value columns. Keys: the characteristics `cols` as the engine stores
+  // them (empty: all F), then n_extra dense device arrays extra_keys [n_extra][T][N] fp32. Values:
+  // the split's returns, then n_values (<= 4) dense device arrays values [n_values][T][N] fp32.
+  // The caller's arrays are read on the engine stream. It reads the panel only -- no model, job
+  // table or graph -- so it runs for every engine shape, the wide layer-0 path included.
+  // Returns count int32 [T][P][Q], sum fp64 [T][P][Q][1 + n_values], breaks fp32 [T][P][Q-1] (NaN
+  // for an empty period), rows (= R) and gpu_ms.
+  py::dict sorted_portfolios(int s, int quantiles, std::vector<int> cols, uintptr_t extra_keys, int n_extra,
+                             uintptr_t values, int n_values) {
+    if (s < 0 || s > 2) throw std::invalid_argument("split must be 0, 1 or 2");
+    if (quantiles < 2 || quantiles > QSORT_MAX_Q) throw std::invalid_argument("sorted_portfolios: quantiles must be in [2, 16]");
+    if (n_values < 0 || n_values > QSORT_MAX_VALUES) throw std::invalid_argument("sorted_portfolios: n_values must be in [0, 4]");
+    if (n_extra < 0 || (n_extra > 0 && !extra_keys)) throw std::invalid_argument("sorted_portfolios: n_extra needs extra_keys");
+    if (n_values > 0 && !values) throw std::invalid_argument("sorted_portfolios: n_values needs values");
+    for (int c : cols)
+      if (c < 0 || c >= md_.F) throw std::invalid_argument("sorted_portfolios: column outside [0, F)");
+    const SplitDev& D = splits_[s];
+    if (!D.set) throw std::runtime_error("split not set");
+    const int Q = quantiles, K1 = 1 + n_values, C = cols.empty() ? md_.F : (int)cols.size(), P = C + n_extra;
+    if (D.T > 65535) throw std::invalid_argument("sorted_portfolios: more than 65535 periods");
+    py::array_t<int> cnt({D.T, P, Q});
+    py::array_t<double> sum({D.T, P, Q, K1});
+    py::array_t<float> brk({D.T, P, Q - 1});
+    std::fill_n(cnt.mutable_data(), cnt.size(), 0);
+    std::fill_n(sum.mutable_data(), sum.size(), 0.0);
+    std::fill_n(brk.mutable_data(), brk.size(), std::nanf(""));
+    float ms = 0.f;
+    if (D.R > 0 && D.T > 0 && P > 0) {        // (an empty split launches nothing and reads nothing)
+      DevBuf<int> dcols, dcnt;
+      DevBuf<double> dsum;
+      DevBuf<float> dbrk;
+      if (!cols.empty()) up(dcols, cols.data(), cols.size());
+      dcnt.alloc((size_t)cnt.size(), false); dsum.alloc((size_t)sum.size(), false); dbrk.alloc((size_t)brk.size(), false);
+      QsortArgs A{};
+      A.X = D.X.p; A.KP = md_.KP; A.fp32 = md_.md.fp32 ? 1 : 0;
+      A.Rc = D.Rc.p; A.rowti = reinterpret_cast<const int2*>(D.rowti.p); A.row_ptr = D.row_ptr.p;
+      A.T = D.T; A.N = D.N; A.Q = Q; A.C = C; A.cols = dcols.p; A.E = n_extra;
+      A.extra = reinterpret_cast<const float*>(extra_keys);
+      A.K = n_values; A.values = reinterpret_cast<const float*>(values);
+      A.count = dcnt.p; A.sum = dsum.p; A.breaks = dbrk.p;
+      hipEvent_t ev[2];
+      for (auto& e : ev) HIP_OK(hipEventCreate(&e));
+      HIP_OK(hipEventRecord(ev[0], st_));
+      launch_qsort_port(A, st_);
+      HIP_OK(hipEventRecord(ev[1], st_));
+      sync();
+      HIP_OK(hipEventElapsedTime(&ms, ev[0], ev[1]));
+      for (auto& e : ev) HIP_OK(hipEventDestroy(e));
+      HIP_LEGACY(hipMemcpy(cnt.mutable_data(), dcnt.p, cnt.size() * sizeof(int), hipMemcpyDeviceToHost));
+      HIP_LEGACY(hipMemcpy(sum.mutable_data(), dsum.p, sum.size() * sizeof(double), hipMemcpyDeviceToHost));
+      if (brk.size()) HIP_LEGACY(hipMemcpy(brk.mutable_data(), dbrk.p, brk.size() * sizeof(float), hipMemcpyDeviceToHost));
+    }
+    py::dict d;
+    d["count"] = cnt; d["sum"] = sum; d["breaks"] = brk; d["rows"] = D.R; d["gpu_ms"] = ms;
     return d;
   }
   void train_step(int phase, float lr) {
@@ -2593,6 +2652,9 @@ PYBIND11_MODULE(_dlap_hip, m) {
       .def("macro_sensitivity", &Engine::macro_sensitivity, py::arg("s"), py::arg("scale") = 0, py::arg("lags") = 1,
            py::arg("refresh") = true)
       .def("macro_sens_supported", [](Engine& e) { return e.macro_sens_ok(); })
+      .def("sorted_portfolios", &Engine::sorted_portfolios, py::arg("s"), py::arg("quantiles") = 10,
+           py::arg("cols") = std::vector<int>{}, py::arg("extra_keys") = 0, py::arg("n_extra") = 0,
+           py::arg("values") = 0, py::arg("n_values") = 0)
       .def("train_step", &Engine::train_step)
       .def("backward_only", &Engine::backward_only, py::arg("phase"), py::arg("wait") = true)
       .def("set_stream", &Engine::set_stream, py::arg("stream"), py::arg("external") = true)

@@ -49,17 +49,18 @@ def get_weights_from_model(model, data: Dict, device: str = "cpu") -> np.ndarray
     return w.detach().cpu().numpy()
 
 
-def weights_batched_gpu(models: Sequence, batches: Dict[str, Dict]) -> Dict[str, torch.Tensor]:
+def weights_batched_gpu(models: Sequence, batches: Dict[str, Dict],
+                        splits: Sequence[str] = SPLITS) -> Dict[str, torch.Tensor]:
     """L1-normalised weights of every model on every split as CUDA tensors [G, T, N] (model
     order), one batched engine forward per split for each group of models that share an
     architecture. Everything stays on the device: the engine's ``wn`` buffers are copied
     device-to-device into the stack (ordered after torch's stream with events, no host sync) and
-    normalised there."""
+    normalised there. ``splits``: the keys of ``batches`` to evaluate (at most three)."""
     from ..engine.runner import GANEngine
     dev = torch.device("cuda", torch.cuda.current_device())
     ts = torch.cuda.current_stream(dev).cuda_stream
     out = {}
-    for split in SPLITS:
+    for split in splits:
         T, N = batches[split]["mask"].shape
         out[split] = torch.empty(len(models), T, N, dtype=torch.float32, device=dev)
     groups: Dict[object, List[int]] = {}
@@ -67,18 +68,18 @@ def weights_batched_gpu(models: Sequence, batches: Dict[str, Dict]) -> Dict[str,
         groups.setdefault(m.spec, []).append(i)
     for spec, idx in groups.items():
         eng = GANEngine(spec, len(idx), max_epochs=4)
-        eng.set_data(batches["train"], batches["valid"], batches["test"])
+        eng.set_data(*[batches[split] for split in splits])
         for g, i in enumerate(idx):
             eng.set_model(g, models[i], 0)
         e = eng.eng
         e.join_from(ts)
-        for s, split in enumerate(SPLITS):
+        for s, split in enumerate(splits):
             e.forward_split(s, False, False)
             for g, i in enumerate(idx):
                 e.copy_ws(g, s, "wn", out[split][i].data_ptr())
         e.join_to(ts)
         e.sync()         # the engine (and its buffers) may be freed after this group
-    for split in SPLITS:                 # per (model, period) L1 normalisation over the stocks
+    for split in splits:                 # per (model, period) L1 normalisation over the stocks
         m = batches[split]["mask"].to(dev).float()
         W = out[split]
         out[split] = W / (W.abs() * m[None]).sum(dim=2, keepdim=True).clamp(min=1e-8)
@@ -88,14 +89,19 @@ def weights_batched_gpu(models: Sequence, batches: Dict[str, Dict]) -> Dict[str,
 def evaluate_ensemble(checkpoint_dirs: Sequence[str], data_dir: str, device: str = "cpu",
                       verbose: bool = True, paper: bool = False, importance: bool = False,
                       importance_split: str = "test", importance_out: str = None,
-                      importance_macro_lags: int = 0) -> Dict:
+                      importance_macro_lags: int = 0, sorted_portfolios: bool = False,
+                      sort_split: str = "test", sort_quantiles: int = 10, sort_out: str = None) -> Dict:
     """Reference output and return value; ``paper=True`` (CLI ``--paper_metrics``) adds the
     paper's EV / XS-R² / turnover / max 1-month loss of the ensemble's SDF factor per split;
     ``importance=True`` (CLI ``--variable_importance``) adds the sensitivity ranking of the
     ensemble weight on ``importance_split`` (``analysis.importance``) under the key
     ``variable_importance`` and writes it to ``importance_out`` (JSON) when given;
     ``importance_macro_lags = L > 0`` (CLI ``--importance_macro_lags``) adds the importance of
-    the macro series through the LSTM for the lags 0 .. L-1 to that ranking."""
+    the macro series through the LSTM for the lags 0 .. L-1 to that ranking;
+    ``sorted_portfolios=True`` (CLI ``--sorted_portfolios``) adds the quantile portfolios of
+    ``sort_split`` sorted on every characteristic and on the ensemble weight, priced by the SDF
+    (``analysis.sorted_portfolios``), under the key ``sorted_portfolios`` and writes them to
+    ``sort_out`` (JSON) when given."""
     say = print if verbose else (lambda *a, **k: None)
     bar = "=" * 70
     say(bar); say(f"ENSEMBLE EVALUATION ({len(checkpoint_dirs)} models, averaged weights)"); say(bar); say()
@@ -169,6 +175,29 @@ def evaluate_ensemble(checkpoint_dirs: Sequence[str], data_dir: str, device: str
             with open(importance_out, "w") as fh:
                 json.dump(to_json(imp), fh, indent=1)
             say(f"  Saved: {importance_out}"); say()
+    if sorted_portfolios:
+        from . import sorted_portfolios as sp
+        if sort_split not in SPLITS:
+            raise ValueError(f"sort_split must be one of {SPLITS}")
+        ds = datasets[SPLITS.index(sort_split)]
+        b = batches[sort_split]
+        if str(device).startswith("cuda"):
+            wavg = average_weights(list(wdev[sort_split].cpu().numpy()), np_batches[sort_split]["mask"])
+        else:
+            wavg = average_weights([w[sort_split] for w in weights], np_batches[sort_split]["mask"])
+        res_sp = sp.sorted_portfolios(models, b, device=device, quantiles=sort_quantiles,
+                                      names=getattr(ds, "variable_names", None), weights=wavg)
+        priced = sp.price_portfolios(res_sp, wavg, np_batches[sort_split]["returns"], np_batches[sort_split]["mask"])
+        out["sorted_portfolios"] = {"portfolios": res_sp, "priced": priced}
+        say(bar); say(f"SORTED PORTFOLIOS ({sort_split} split, {res_sp['quantiles']} buckets, equally weighted)")
+        say(bar); say()
+        for line in sp.format_sorted(priced):
+            say(line)
+        say()
+        if sort_out:
+            with open(sort_out, "w") as fh:
+                json.dump(sp.to_json(res_sp, priced), fh, indent=1)
+            say(f"  Saved: {sort_out}"); say()
     return out
 
 
@@ -184,8 +213,15 @@ def main(argv=None):
     p.add_argument("--importance_out", type=str, default=None, help="write the ranking to FILE.json")
     p.add_argument("--importance_macro_lags", type=int, default=0,
                    help="with --variable_importance: also rank the macro series through the LSTM, lags 0..L-1")
+    p.add_argument("--sorted_portfolios", action="store_true",
+                   help="also price the quantile portfolios sorted on every characteristic and on the weight")
+    p.add_argument("--sort_split", type=str, default="test", choices=SPLITS)
+    p.add_argument("--sort_quantiles", type=int, default=10, help="buckets per sort (2..16)")
+    p.add_argument("--sort_out", type=str, default=None, help="write the sorted-portfolio results to FILE.json")
     a = p.parse_args(argv)
     kw = {"importance_macro_lags": a.importance_macro_lags} if a.importance_macro_lags else {}
+    if a.sorted_portfolios:
+        kw.update(sorted_portfolios=True, sort_split=a.sort_split, sort_quantiles=a.sort_quantiles, sort_out=a.sort_out)
     return evaluate_ensemble(a.checkpoint_dirs, a.data_dir, a.device, paper=a.paper_metrics,
                              importance=a.variable_importance, importance_split=a.importance_split,
                              importance_out=a.importance_out, **kw)
