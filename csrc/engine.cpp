@@ -45,6 +45,7 @@
 #include "rnn.h"
 #include "update.h"
 #include "wide.h"
+#include "wsurf.h"
 
 namespace py = pybind11;
 
@@ -935,6 +936,86 @@ class Engine {
     }
     py::dict d;
     d["count"] = cnt; d["sum"] = sum; d["breaks"] = brk; d["rows"] = D.R; d["gpu_ms"] = ms;
+    return d;
+  }
+  // SDF weight structure of split s (k_wsurf.hip, definition in wsurf.h): the raw weight of the
+  // base row with the characteristics of each item moved over the grid, summed over the split's
+  // periods and the models with the factors `scale` (device fp32 [G][T], 0: ones; read on the
+  // engine stream). items: (a, -1) curves first, then (a, b) surfaces. Returns values float32
+  // [rows] (P per curve, P * P per surface with the second column's index fastest), rows,
+  // gpu_ms, and tiles_per_wave / period_split (the launch's chunking; the values do not depend on it). Argument errors are std::invalid_argument. refresh as for input_sensitivity.
+  bool wsurf_ok(int s) const {
+    return s >= 0 && s <= 2 && splits_[s].set && wsurf_supported(md_.md, md_.KS1, splits_[s].T);
+  }
+  py::dict weight_surface(int s, uintptr_t scale, std::vector<float> grid, std::vector<float> base,
+                          std::vector<std::pair<int, int>> items, bool refresh = true) {
+    if (s < 0 || s > 2) throw std::invalid_argument("weight_surface: split must be 0, 1 or 2");
+    const int P = (int)grid.size(), F = md_.F;
+    if (grid.size() < 2 || grid.size() > WSURF_MAX_P) throw std::invalid_argument("weight_surface: the grid must have 2 .. 64 points");
+    if ((int)base.size() != F) throw std::invalid_argument("weight_surface: base must have F entries");
+    if (items.empty()) throw std::invalid_argument("weight_surface: no items");
+    int n1 = 0, n2 = 0;
+    for (const auto& it : items) {
+      if (it.first < 0 || it.first >= F || it.second < -1 || it.second >= F)
+        throw std::invalid_argument("weight_surface: column outside [0, F)");
+      if (it.first == it.second) throw std::invalid_argument("weight_surface: a surface needs two different columns");
+      if (it.second < 0 && n2 > 0) throw std::invalid_argument("weight_surface: curves go before surfaces");
+      (it.second < 0 ? n1 : n2)++;
+    }
+    const long long rows = (long long)n1 * P + (long long)n2 * P * P;
+    if (rows > (1ll << 30)) throw std::invalid_argument("weight_surface: more than 2^30 rows");
+    if (!splits_[s].set) throw std::invalid_argument("weight_surface: split not set");
+    ensure_jobs();
+    const SplitDev& D = splits_[s];
+    if (!wsurf_supported(md_.md, md_.KS1, D.T))
+      throw std::invalid_argument("weight_surface: not available for this shape (wide layer-0 path, or the "
+                                  "fragments and per-period inputs exceed the LDS budget)");
+    if (D.R <= 0) throw std::invalid_argument("weight_surface: the split has no valid rows");
+    if (refresh) fwd_only(s, false, false, false);
+    // buffers of this call (an analysis pass, not a step of an epoch), released on return, after
+    // the final sync
+    DevBuf<char> tj;
+    DevBuf<float> scl, dgrid, dbase, res;
+    DevBuf<int2> ditems;
+    const size_t ns = (size_t)G_ * D.T;
+    scl.alloc(ns, false);
+    if (scale) {
+      HIP_OK(hipMemcpyAsync(scl.p, reinterpret_cast<const void*>(scale), ns * sizeof(float),
+                            hipMemcpyDeviceToDevice, st_));
+    }
+    sync();
+    if (!scale) {
+      const std::vector<float> ones(ns, 1.f);
+      HIP_LEGACY(hipMemcpy(scl.p, ones.data(), ns * sizeof(float), hipMemcpyHostToDevice));
+    }
+    std::vector<float> hb((size_t)md_.KP, 0.f);
+    std::copy(base.begin(), base.end(), hb.begin());
+    std::vector<int2> hi;
+    for (const auto& it : items) hi.push_back(int2{it.first, it.second});
+    up(dgrid, grid.data(), grid.size());
+    up(dbase, hb.data(), hb.size());
+    up(ditems, hi.data(), hi.size());
+    std::vector<MlpJob> mj;
+    for (int g = 0; g < G_; ++g) mj.push_back(mlp_job(g, s, false, true, false));
+    upload(tj, mj);
+    res.alloc((size_t)rows, false);
+    WsurfArgs A{};
+    A.scale = scl.p; A.grid = dgrid.p; A.base = dbase.p; A.items = ditems.p;
+    A.n1 = n1; A.n2 = n2; A.P = P; A.rows = (int)rows; A.G = G_; A.T = D.T; A.out = res.p;
+    float ms = 0.f;
+    hipEvent_t ev[2];
+    for (auto& e : ev) HIP_OK(hipEventCreate(&e));
+    HIP_OK(hipEventRecord(ev[0], st_));
+    const WsurfPlan plan = launch_weight_surface(as<MlpJob>(tj), A, md_.md, md_.KS1, st_);
+    HIP_OK(hipEventRecord(ev[1], st_));
+    sync();
+    HIP_OK(hipEventElapsedTime(&ms, ev[0], ev[1]));
+    for (auto& e : ev) HIP_OK(hipEventDestroy(e));
+    py::array_t<float> vals((py::ssize_t)rows);
+    HIP_LEGACY(hipMemcpy(vals.mutable_data(), res.p, (size_t)rows * sizeof(float), hipMemcpyDeviceToHost));
+    py::dict d;
+    d["values"] = vals; d["rows"] = (long long)rows; d["gpu_ms"] = ms; d["tiles_per_wave"] = plan.tiles_per_wave;
+    d["period_split"] = plan.period_split;
     return d;
   }
   void train_step(int phase, float lr) {
@@ -2655,6 +2736,9 @@ PYBIND11_MODULE(_dlap_hip, m) {
       .def("sorted_portfolios", &Engine::sorted_portfolios, py::arg("s"), py::arg("quantiles") = 10,
            py::arg("cols") = std::vector<int>{}, py::arg("extra_keys") = 0, py::arg("n_extra") = 0,
            py::arg("values") = 0, py::arg("n_values") = 0)
+      .def("weight_surface", &Engine::weight_surface, py::arg("s"), py::arg("scale"), py::arg("grid"), py::arg("base"),
+           py::arg("items"), py::arg("refresh") = true)
+      .def("weight_surface_supported", [](Engine& e, int s) { return e.wsurf_ok(s); }, py::arg("s") = 0)
       .def("train_step", &Engine::train_step)
       .def("backward_only", &Engine::backward_only, py::arg("phase"), py::arg("wait") = true)
       .def("set_stream", &Engine::set_stream, py::arg("stream"), py::arg("external") = true)

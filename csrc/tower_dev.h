@@ -353,6 +353,39 @@ DLAP_DEV void issue_rowti(const MlpJob& J, int tile, int2 (&ti)[2]) {
   for (int b = 0; b < 2; ++b) ti[b] = gp(J.rowti)[min(tile * 32 + 16 * b + (l & 15), J.R - 1)];
 }
 
+// SDF tower forward on one tile: the raw (pre-normalisation) weight of each row block.
+// kw[j]: keep word of hidden layer j (ignored unless DROP). layer0_fn(a) fills the layer-0
+// pre-activations including the bias (fused: MFMA over the X tile; wide: from z).
+// Output layer on the matrix cores: the 2 s_wo fragments hold the output row as row 0 of an
+// A operand, so C[0][row] = wo . act + bo lands on the lanes of lane group 0.
+// (Shared by k_mlp.hip's forward kernels and k_wsurf.hip.)
+template <class P, bool DROP, typename L0>
+DLAP_DEV void sdf_forward_tile(const typename P::Frag* lds, const float* aux, const MlpDims& D,
+                               const uint32_t (&kw)[4], L0&& layer0_fn, float (&w)[2]) {
+  f32x4 a[2][4];
+  typename P::Frag pf[2][2];
+  layer0_fn(a);
+  act_tile<P, 4, DROP>(a, kw[0], pf);
+  // fully unrolled to the engine's 4-layer limit so kw[j] is a register, not scratch
+#pragma unroll
+  for (int j = 1; j < 4; ++j) {
+    if (j >= D.nl_sdf) break;
+    layer_chain<P, 4, 2>(lds, D.s_fwd + (j - 1) * 8, pf, a, aux + D.a_sb + 64 * j);
+    act_tile<P, 4, DROP>(a, kw[j], pf);
+  }
+  const int q = lane_id() >> 4;
+  const float bo = aux[D.a_bo];
+  f32x4 c0 = f32x4{q == 0 ? bo : 0.f, 0.f, 0.f, 0.f}, c1 = c0;
+#pragma unroll
+  for (int s = 0; s < 2; ++s) {
+    const typename P::Frag wf = ldsf(lds, D.s_wo + s);
+    c0 = P::mma(wf, pf[0][s], c0);
+    c1 = P::mma(wf, pf[1][s], c1);
+  }
+  w[0] = c0[0];
+  w[1] = c1[0];
+}
+
 DLAP_DEV float reduce_q(float v) {  // sum over the 4 lane groups that share l & 15
   v += __shfl_xor(v, 16, 64);
   v += __shfl_xor(v, 32, 64);

@@ -90,7 +90,9 @@ def evaluate_ensemble(checkpoint_dirs: Sequence[str], data_dir: str, device: str
                       verbose: bool = True, paper: bool = False, importance: bool = False,
                       importance_split: str = "test", importance_out: str = None,
                       importance_macro_lags: int = 0, sorted_portfolios: bool = False,
-                      sort_split: str = "test", sort_quantiles: int = 10, sort_out: str = None) -> Dict:
+                      sort_split: str = "test", sort_quantiles: int = 10, sort_out: str = None,
+                      weight_structure: bool = False, structure_split: str = "test", structure_points: int = 21,
+                      structure_pairs=None, structure_out: str = None) -> Dict:
     """Reference output and return value; ``paper=True`` (CLI ``--paper_metrics``) adds the
     paper's EV / XS-R² / turnover / max 1-month loss of the ensemble's SDF factor per split;
     ``importance=True`` (CLI ``--variable_importance``) adds the sensitivity ranking of the
@@ -101,7 +103,12 @@ def evaluate_ensemble(checkpoint_dirs: Sequence[str], data_dir: str, device: str
     ``sorted_portfolios=True`` (CLI ``--sorted_portfolios``) adds the quantile portfolios of
     ``sort_split`` sorted on every characteristic and on the ensemble weight, priced by the SDF
     (``analysis.sorted_portfolios``), under the key ``sorted_portfolios`` and writes them to
-    ``sort_out`` (JSON) when given."""
+    ``sort_out`` (JSON) when given;
+    ``weight_structure=True`` (CLI ``--weight_structure``) adds the response curves of every
+    characteristic on ``structure_split`` over ``structure_points`` grid points, and the
+    interaction surfaces of ``structure_pairs`` (``"all"``, a list of (a, b), or the CLI's comma
+    list of ``A:B`` by name or column), under the key ``weight_structure``
+    (``analysis.weight_structure``) and writes them to ``structure_out`` (JSON) when given."""
     say = print if verbose else (lambda *a, **k: None)
     bar = "=" * 70
     say(bar); say(f"ENSEMBLE EVALUATION ({len(checkpoint_dirs)} models, averaged weights)"); say(bar); say()
@@ -198,6 +205,24 @@ def evaluate_ensemble(checkpoint_dirs: Sequence[str], data_dir: str, device: str
             with open(sort_out, "w") as fh:
                 json.dump(sp.to_json(res_sp, priced), fh, indent=1)
             say(f"  Saved: {sort_out}"); say()
+    if weight_structure:
+        from . import weight_structure as wst
+        if structure_split not in SPLITS:
+            raise ValueError(f"structure_split must be one of {SPLITS}")
+        ds = datasets[SPLITS.index(structure_split)]
+        b = batches[structure_split]
+        names = getattr(ds, "variable_names", None)
+        res_ws = wst.weight_structure(models, b, device=device, grid=wst.default_grid_base(b, int(structure_points))[0],
+                                      pairs=wst.parse_pairs(structure_pairs, names), names=names)
+        out["weight_structure"] = res_ws
+        say(bar); say(f"WEIGHT STRUCTURE ({structure_split} split, ensemble weight)"); say(bar); say()
+        for line in wst.format_structure(res_ws):
+            say(line)
+        say()
+        if structure_out:
+            with open(structure_out, "w") as fh:
+                json.dump(wst.to_json(res_ws), fh, indent=1)
+            say(f"  Saved: {structure_out}"); say()
     return out
 
 
@@ -218,8 +243,18 @@ def main(argv=None):
     p.add_argument("--sort_split", type=str, default="test", choices=SPLITS)
     p.add_argument("--sort_quantiles", type=int, default=10, help="buckets per sort (2..16)")
     p.add_argument("--sort_out", type=str, default=None, help="write the sorted-portfolio results to FILE.json")
+    p.add_argument("--weight_structure", action="store_true",
+                   help="also compute the response curves (and surfaces) of the ensemble weight")
+    p.add_argument("--structure_split", type=str, default="test", choices=SPLITS)
+    p.add_argument("--structure_points", type=int, default=21, help="grid points per characteristic (2..64)")
+    p.add_argument("--structure_pairs", type=str, default=None,
+                   help="interaction surfaces: 'all' or a comma list of A:B, by name or column index")
+    p.add_argument("--structure_out", type=str, default=None, help="write the curves and surfaces to FILE.json")
     a = p.parse_args(argv)
     kw = {"importance_macro_lags": a.importance_macro_lags} if a.importance_macro_lags else {}
+    if a.weight_structure:
+        kw.update(weight_structure=True, structure_split=a.structure_split, structure_points=a.structure_points,
+                  structure_pairs=a.structure_pairs, structure_out=a.structure_out)
     if a.sorted_portfolios:
         kw.update(sorted_portfolios=True, sort_split=a.sort_split, sort_quantiles=a.sort_quantiles, sort_out=a.sort_out)
     return evaluate_ensemble(a.checkpoint_dirs, a.data_dir, a.device, paper=a.paper_metrics,

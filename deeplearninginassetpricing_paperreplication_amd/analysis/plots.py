@@ -250,8 +250,55 @@ def plot_macro_importance(checkpoint_dirs, data_dir, save_path=None, device: str
     return fig, (ax, bx)
 
 
+def plot_weight_structure(checkpoint_dirs, data_dir, save_path=None, device: str = "cpu", split: str = "test",
+                          top: int = 12, pairs=None, points: int = 21, top_pairs: int = 4, structure: Dict = None):
+    """Response curves of the ``top`` characteristics with the largest curve range and, when pairs
+    were given, the interaction surfaces of the ``top_pairs`` pairs with the largest departure from
+    additivity as filled contours (group 0 of ``analysis.weight_structure``)."""
+    if structure is None:
+        from .weight_structure import default_grid_base, parse_pairs, weight_structure
+        ds = load_splits(data_dir)[SPLITS.index(split)]
+        models = [load_model(d, "cpu")[0] for d in checkpoint_dirs]
+        names = getattr(ds, "variable_names", None)
+        batch = ds.get_full_batch()
+        structure = weight_structure(models, batch, device=device, grid=default_grid_base(batch, points)[0],
+                                     pairs=parse_pairs(pairs, names), names=names)
+    grid, names = np.asarray(structure["grid"]), structure["names"]
+    curves = np.asarray(structure["curves"])[0] - float(np.asarray(structure["offset"])[0])
+    surfaces, inter = np.asarray(structure["surfaces"])[0], np.asarray(structure["interaction"])[0]
+    rng = curves.max(1) - curves.min(1) if len(curves) else np.zeros(0)
+    order = np.argsort(-rng)[:top]
+    porder = np.argsort(-np.nan_to_num(inter, nan=-1.0))[:top_pairs] if len(inter) else []
+    ncol = 4
+    nrow_c = max(1, -(-len(order) // ncol))
+    nrow = nrow_c + (1 if len(porder) else 0)
+    fig, axes = plt.subplots(nrow, ncol, figsize=(4 * ncol, 3 * nrow), squeeze=False)
+    for ax in axes.ravel():
+        ax.set_visible(False)
+    for i, j in enumerate(order):
+        ax = axes[i // ncol][i % ncol]
+        ax.set_visible(True)
+        ax.plot(grid, curves[j], color="steelblue", linewidth=2)
+        ax.axhline(0.0, color="black", linewidth=0.5)
+        ax.set_title(names[structure["curve_items"][j]], fontsize=10)
+        ax.grid(True, alpha=0.3)
+    for i, j in enumerate(porder):
+        ax = axes[nrow_c][i]
+        ax.set_visible(True)
+        a, b = structure["pair_items"][j]
+        cs = ax.contourf(grid, grid, surfaces[j] - float(np.asarray(structure["offset"])[0]), levels=12, cmap="RdBu_r")
+        fig.colorbar(cs, ax=ax)
+        ax.set(xlabel=names[b], ylabel=names[a])
+        ax.set_title(f"{names[a]} x {names[b]}", fontsize=10)
+    fig.suptitle(f"SDF weight structure ({split}): weight against one and two characteristics", fontsize=13)
+    fig.tight_layout()
+    _save(fig, save_path)
+    return fig, axes
+
+
 def generate_all_plots(checkpoint_dirs, data_dir, output_dir="./plots", device: str = "cpu",
-                       variable_importance: bool = False, importance_macro_lags: int = 0):
+                       variable_importance: bool = False, importance_macro_lags: int = 0,
+                       weight_structure: bool = False, structure_pairs=None):
     os.makedirs(output_dir, exist_ok=True)
     print("Generating plots...")
     print("=" * 50)
@@ -274,6 +321,10 @@ def generate_all_plots(checkpoint_dirs, data_dir, output_dir="./plots", device: 
             jobs.append(("Macro Importance", "macro_importance.png",
                          lambda p: plot_macro_importance(checkpoint_dirs, data_dir, p, device=device,
                                                          lags=importance_macro_lags)))
+    if weight_structure:
+        jobs.append(("Weight Structure", "weight_structure.png",
+                     lambda p: plot_weight_structure(checkpoint_dirs, data_dir, p, device=device,
+                                                     pairs=structure_pairs)))
     for i, (title, fname, fn) in enumerate(jobs, 1):
         print(f"\n{i}. {title}...")
         fn(os.path.join(output_dir, fname))
@@ -293,14 +344,21 @@ def main(argv=None):
                    help="also write variable_importance.png (top 20 characteristics)")
     p.add_argument("--importance_macro_lags", type=int, default=0,
                    help="with --variable_importance: also write macro_importance.png for the lags 0..L-1")
+    p.add_argument("--weight_structure", action="store_true",
+                   help="also write weight_structure.png (response curves of the 12 widest characteristics)")
+    p.add_argument("--structure_pairs", type=str, default=None,
+                   help="with --weight_structure: 'all' or a comma list of A:B (name or column), adds the surfaces")
     a = p.parse_args(argv)
+    kw = {}
+    if a.weight_structure:
+        kw = dict(weight_structure=True, structure_pairs=a.structure_pairs)
     if a.variable_importance and a.importance_macro_lags > 0:
         generate_all_plots(a.checkpoint_dirs, a.data_dir, a.output_dir, a.device, variable_importance=True,
-                           importance_macro_lags=a.importance_macro_lags)
+                           importance_macro_lags=a.importance_macro_lags, **kw)
     elif a.variable_importance:
-        generate_all_plots(a.checkpoint_dirs, a.data_dir, a.output_dir, a.device, variable_importance=True)
+        generate_all_plots(a.checkpoint_dirs, a.data_dir, a.output_dir, a.device, variable_importance=True, **kw)
     else:
-        generate_all_plots(a.checkpoint_dirs, a.data_dir, a.output_dir, a.device)
+        generate_all_plots(a.checkpoint_dirs, a.data_dir, a.output_dir, a.device, **kw)
 
 
 if __name__ == "__main__":
