@@ -42,6 +42,7 @@
 #include "mlp.h"
 #include "panel.h"
 #include "qsort.h"
+#include "qsort2.h"
 #include "rnn.h"
 #include "update.h"
 #include "wide.h"
@@ -936,6 +937,73 @@ class Engine {
     }
     py::dict d;
     d["count"] = cnt; d["sum"] = sum; d["breaks"] = brk; d["rows"] = D.R; d["gpu_ms"] = ms;
+    return d;
+  }
+  // Double-sorted portfolios of split s (k_qsort2.hip, definition in qsort2.h): per period and pair
+  // (A, B) of key indices a qa x qb two-way quantile sort; conditional: B's breakpoints within each
+  // A bucket, else over the whole period. A key index k < F is characteristic k as the engine
+  // stores it, F + e the dense device array e of extra_keys [n_extra][T][N] fp32. Values: the
+  // split's returns, then n_values (<= 2) dense device arrays values [n_values][T][N] fp32. The
+  // caller's arrays are read on the engine stream. Like sorted_portfolios it reads the panel only.
+  // Returns count int32 [T][P][qa][qb], sum fp64 [T][P][qa][qb][1 + n_values], breaks_a fp32
+  // [T][P][qa-1], breaks_b fp32 [T][P][qa][qb-1] (NaN where the period or the A bucket is empty),
+  // rows (= R) and gpu_ms. An empty pair list returns empty arrays and launches nothing.
+  py::dict double_sorted_portfolios(int s, std::vector<std::pair<int, int>> pairs, int qa, int qb, bool conditional,
+                                    uintptr_t extra_keys, int n_extra, uintptr_t values, int n_values) {
+    if (s < 0 || s > 2) throw std::invalid_argument("split must be 0, 1 or 2");
+    if (qa < 2 || qa > QSORT2_MAX_Q || qb < 2 || qb > QSORT2_MAX_Q)
+      throw std::invalid_argument("double_sorted_portfolios: qa and qb must be in [2, 16]");
+    if (qa * qb > QSORT2_MAX_CELLS) throw std::invalid_argument("double_sorted_portfolios: qa * qb must be at most 36");
+    if (n_values < 0 || n_values > QSORT2_MAX_VALUES) throw std::invalid_argument("double_sorted_portfolios: n_values must be in [0, 2]");
+    if (n_extra < 0 || (n_extra > 0 && !extra_keys)) throw std::invalid_argument("double_sorted_portfolios: n_extra needs extra_keys");
+    if (n_values > 0 && !values) throw std::invalid_argument("double_sorted_portfolios: n_values needs values");
+    for (const auto& pr : pairs)
+      if (pr.first < 0 || pr.first >= md_.F + n_extra || pr.second < 0 || pr.second >= md_.F + n_extra)
+        throw std::invalid_argument("double_sorted_portfolios: key index outside [0, F + n_extra)");
+    const SplitDev& D = splits_[s];
+    if (!D.set) throw std::runtime_error("split not set");
+    if (D.T > 65535) throw std::invalid_argument("double_sorted_portfolios: more than 65535 periods");
+    const int K1 = 1 + n_values, P = (int)pairs.size();
+    py::array_t<int> cnt({D.T, P, qa, qb});
+    py::array_t<double> sum({D.T, P, qa, qb, K1});
+    py::array_t<float> bra({D.T, P, qa - 1}), brb({D.T, P, qa, qb - 1});
+    std::fill_n(cnt.mutable_data(), cnt.size(), 0);
+    std::fill_n(sum.mutable_data(), sum.size(), 0.0);
+    std::fill_n(bra.mutable_data(), bra.size(), std::nanf(""));
+    std::fill_n(brb.mutable_data(), brb.size(), std::nanf(""));
+    float ms = 0.f;
+    if (D.R > 0 && D.T > 0 && P > 0) {        // (an empty split or pair list launches nothing)
+      std::vector<int> flat;
+      for (const auto& pr : pairs) { flat.push_back(pr.first); flat.push_back(pr.second); }
+      DevBuf<int> dpairs, dcnt;
+      DevBuf<double> dsum;
+      DevBuf<float> dbra, dbrb;
+      up(dpairs, flat.data(), flat.size());
+      dcnt.alloc((size_t)cnt.size(), false); dsum.alloc((size_t)sum.size(), false);
+      dbra.alloc((size_t)bra.size(), false); dbrb.alloc((size_t)brb.size(), false);
+      Qsort2Args A{};
+      A.X = D.X.p; A.KP = md_.KP; A.fp32 = md_.md.fp32 ? 1 : 0;
+      A.Rc = D.Rc.p; A.rowti = reinterpret_cast<const int2*>(D.rowti.p); A.row_ptr = D.row_ptr.p;
+      A.T = D.T; A.N = D.N; A.F = md_.F; A.P = P; A.pairs = reinterpret_cast<const int2*>(dpairs.p);
+      A.Qa = qa; A.Qb = qb; A.conditional = conditional ? 1 : 0;
+      A.E = n_extra; A.extra = reinterpret_cast<const float*>(extra_keys);
+      A.K = n_values; A.values = reinterpret_cast<const float*>(values);
+      A.count = dcnt.p; A.sum = dsum.p; A.breaks_a = dbra.p; A.breaks_b = dbrb.p;
+      hipEvent_t ev[2];
+      for (auto& e : ev) HIP_OK(hipEventCreate(&e));
+      HIP_OK(hipEventRecord(ev[0], st_));
+      launch_qsort2_port(A, st_);
+      HIP_OK(hipEventRecord(ev[1], st_));
+      sync();
+      HIP_OK(hipEventElapsedTime(&ms, ev[0], ev[1]));
+      for (auto& e : ev) HIP_OK(hipEventDestroy(e));
+      HIP_LEGACY(hipMemcpy(cnt.mutable_data(), dcnt.p, cnt.size() * sizeof(int), hipMemcpyDeviceToHost));
+      HIP_LEGACY(hipMemcpy(sum.mutable_data(), dsum.p, sum.size() * sizeof(double), hipMemcpyDeviceToHost));
+      HIP_LEGACY(hipMemcpy(bra.mutable_data(), dbra.p, bra.size() * sizeof(float), hipMemcpyDeviceToHost));
+      HIP_LEGACY(hipMemcpy(brb.mutable_data(), dbrb.p, brb.size() * sizeof(float), hipMemcpyDeviceToHost));
+    }
+    py::dict d;
+    d["count"] = cnt; d["sum"] = sum; d["breaks_a"] = bra; d["breaks_b"] = brb; d["rows"] = D.R; d["gpu_ms"] = ms;
     return d;
   }
   // SDF weight structure of split s (k_wsurf.hip, definition in wsurf.h): the raw weight of the
@@ -2736,6 +2804,9 @@ PYBIND11_MODULE(_dlap_hip, m) {
       .def("sorted_portfolios", &Engine::sorted_portfolios, py::arg("s"), py::arg("quantiles") = 10,
            py::arg("cols") = std::vector<int>{}, py::arg("extra_keys") = 0, py::arg("n_extra") = 0,
            py::arg("values") = 0, py::arg("n_values") = 0)
+      .def("double_sorted_portfolios", &Engine::double_sorted_portfolios, py::arg("s"), py::arg("pairs"),
+           py::arg("qa") = 5, py::arg("qb") = 5, py::arg("conditional") = true, py::arg("extra_keys") = 0,
+           py::arg("n_extra") = 0, py::arg("values") = 0, py::arg("n_values") = 0)
       .def("weight_surface", &Engine::weight_surface, py::arg("s"), py::arg("scale"), py::arg("grid"), py::arg("base"),
            py::arg("items"), py::arg("refresh") = true)
       .def("weight_surface_supported", [](Engine& e, int s) { return e.wsurf_ok(s); }, py::arg("s") = 0)

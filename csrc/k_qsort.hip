@@ -38,6 +38,7 @@
 // An empty period writes its zero counts / sums and NaN breakpoints and reads no row.
 #include "common.h"
 #include "qsort.h"
+#include "qsort_dev.h"             // qkey_u32, qkey_f32, qkey_load
 
 #define QNT 256
 #define QNB (QSORT_MAX_Q - 1)
@@ -47,32 +48,6 @@
 #define QMAXV (1 + QSORT_MAX_VALUES)
 #define QUC 8                      // rows a lane loads before it processes them: count sweeps,
 #define QUA 4                      // assign sweep (one load latency per batch instead of per row)
-
-DLAP_DEV uint32_t qkey_u32(float x) {
-  uint32_t b = __float_as_uint(x);
-  b = b == 0x80000000u ? 0u : b;                       // -0.0 -> +0.0
-  return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);
-}
-// the key's value; k16: a 16-bit (bf16) key in the high half
-DLAP_DEV float qkey_f32(uint32_t u, bool k16) {
-  if (k16) return __uint_as_float((u ^ ((u >> 31) ? 0x80000000u : 0xFFFF0000u)) & 0xFFFF0000u);
-  return __uint_as_float(u ^ ((u >> 31) ? 0x80000000u : 0xFFFFFFFFu));
-}
-
-// key of compact row r: panel column col of a characteristic block, else the dense array ext [N]
-template <bool F32>
-DLAP_DEV uint32_t qkey_load(const QsortArgs& a, bool is_char, int col, const float* ext, int r) {
-  if (is_char) {
-    if constexpr (F32) return qkey_u32(gp(reinterpret_cast<const float*>(a.X))[(size_t)r * a.KP + col]);
-    else {
-      uint32_t h = gp(reinterpret_cast<const u16*>(a.X))[(size_t)r * a.KP + col];
-      h = h == 0x8000u ? 0u : h;
-      return (h ^ ((h >> 15) ? 0xFFFFu : 0x8000u)) << 16;
-    }
-  }
-  const int i = gp(a.rowti)[r].y;
-  return qkey_u32(gp(ext)[i]);
-}
 
 template <bool F32, int K1>
 __global__ __launch_bounds__(QNT) void k_qsort_port(QsortArgs a) {

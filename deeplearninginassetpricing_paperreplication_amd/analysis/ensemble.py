@@ -92,7 +92,8 @@ def evaluate_ensemble(checkpoint_dirs: Sequence[str], data_dir: str, device: str
                       importance_macro_lags: int = 0, sorted_portfolios: bool = False,
                       sort_split: str = "test", sort_quantiles: int = 10, sort_out: str = None,
                       weight_structure: bool = False, structure_split: str = "test", structure_points: int = 21,
-                      structure_pairs=None, structure_out: str = None) -> Dict:
+                      structure_pairs=None, structure_out: str = None, double_sorts=None,
+                      double_quantiles=(5, 5), double_mode: str = "conditional", double_out: str = None) -> Dict:
     """Reference output and return value; ``paper=True`` (CLI ``--paper_metrics``) adds the
     paper's EV / XS-R² / turnover / max 1-month loss of the ensemble's SDF factor per split;
     ``importance=True`` (CLI ``--variable_importance``) adds the sensitivity ranking of the
@@ -108,7 +109,12 @@ def evaluate_ensemble(checkpoint_dirs: Sequence[str], data_dir: str, device: str
     characteristic on ``structure_split`` over ``structure_points`` grid points, and the
     interaction surfaces of ``structure_pairs`` (``"all"``, a list of (a, b), or the CLI's comma
     list of ``A:B`` by name or column), under the key ``weight_structure``
-    (``analysis.weight_structure``) and writes them to ``structure_out`` (JSON) when given."""
+    (``analysis.weight_structure``) and writes them to ``structure_out`` (JSON) when given;
+    ``double_sorts`` (CLI ``--double_sorts``: a list of (A, B), or the CLI's comma list of ``A:B`` by
+    name, column or ``weight``) adds the ``double_quantiles`` = (Qa, Qb) double-sorted portfolios
+    of ``sort_split`` (``double_mode``: ``conditional`` or ``independent``), priced by the SDF
+    (``analysis.sorted_portfolios.double_sorted_portfolios``), under the key ``double_sorts`` and
+    writes them to ``double_out`` (JSON) when given."""
     say = print if verbose else (lambda *a, **k: None)
     bar = "=" * 70
     say(bar); say(f"ENSEMBLE EVALUATION ({len(checkpoint_dirs)} models, averaged weights)"); say(bar); say()
@@ -205,6 +211,37 @@ def evaluate_ensemble(checkpoint_dirs: Sequence[str], data_dir: str, device: str
             with open(sort_out, "w") as fh:
                 json.dump(sp.to_json(res_sp, priced), fh, indent=1)
             say(f"  Saved: {sort_out}"); say()
+    if double_sorts:
+        from . import sorted_portfolios as sp
+        from .weight_structure import parse_pairs
+        if sort_split not in SPLITS:
+            raise ValueError(f"sort_split must be one of {SPLITS}")
+        if double_mode not in ("conditional", "independent"):
+            raise ValueError("double_mode must be conditional or independent")
+        ds = datasets[SPLITS.index(sort_split)]
+        b = batches[sort_split]
+        F = int(b["individual_features"].shape[2])
+        names = getattr(ds, "variable_names", None)
+        keyn = ([str(n) for n in names] if names is not None and len(names) == F else [str(j) for j in range(F)]) + ["weight"]
+        if str(device).startswith("cuda"):
+            wavg = average_weights(list(wdev[sort_split].cpu().numpy()), np_batches[sort_split]["mask"])
+        else:
+            wavg = average_weights([w[sort_split] for w in weights], np_batches[sort_split]["mask"])
+        res_ds = sp.double_sorted_portfolios(models, b, parse_pairs(double_sorts, keyn), device=device,
+                                             quantiles=sp.parse_double_quantiles(double_quantiles),
+                                             conditional=double_mode == "conditional", names=names, weights=wavg)
+        priced = sp.price_double_sorted(res_ds, wavg, np_batches[sort_split]["returns"], np_batches[sort_split]["mask"])
+        out["double_sorts"] = {"portfolios": res_ds, "priced": priced}
+        qa, qb = res_ds["quantiles"]
+        say(bar); say(f"DOUBLE-SORTED PORTFOLIOS ({sort_split} split, {qa} x {qb} cells, {res_ds['mode']}, equally weighted)")
+        say(bar); say()
+        for line in sp.format_double_sorted(priced):
+            say(line)
+        say()
+        if double_out:
+            with open(double_out, "w") as fh:
+                json.dump(sp.double_to_json(res_ds, priced), fh, indent=1)
+            say(f"  Saved: {double_out}"); say()
     if weight_structure:
         from . import weight_structure as wst
         if structure_split not in SPLITS:
@@ -226,7 +263,7 @@ def evaluate_ensemble(checkpoint_dirs: Sequence[str], data_dir: str, device: str
     return out
 
 
-def main(argv=None):
+def _parser():
     p = argparse.ArgumentParser(description="Evaluate an ensemble by averaging SDF weights")
     p.add_argument("--data_dir", type=str, required=True)
     p.add_argument("--checkpoint_dirs", type=str, nargs="+", required=True)
@@ -250,13 +287,32 @@ def main(argv=None):
     p.add_argument("--structure_pairs", type=str, default=None,
                    help="interaction surfaces: 'all' or a comma list of A:B, by name or column index")
     p.add_argument("--structure_out", type=str, default=None, help="write the curves and surfaces to FILE.json")
-    a = p.parse_args(argv)
+    p.add_argument("--double_sorts", type=str, default=None,
+                   help="double-sorted portfolios on --sort_split: a comma list of A:B, by name, column index or 'weight'")
+    p.add_argument("--double_quantiles", type=str, default="5x5", help="QAxQB buckets (2..16 each, at most 36 cells)")
+    p.add_argument("--double_mode", type=str, default="conditional", choices=("conditional", "independent"))
+    p.add_argument("--double_out", type=str, default=None, help="write the double-sorted results to FILE.json")
+    return p
+
+
+def _extra_kwargs(a) -> Dict:
+    """The optional blocks' keyword arguments of ``evaluate_ensemble`` from the parsed flags."""
     kw = {"importance_macro_lags": a.importance_macro_lags} if a.importance_macro_lags else {}
     if a.weight_structure:
         kw.update(weight_structure=True, structure_split=a.structure_split, structure_points=a.structure_points,
                   structure_pairs=a.structure_pairs, structure_out=a.structure_out)
     if a.sorted_portfolios:
         kw.update(sorted_portfolios=True, sort_split=a.sort_split, sort_quantiles=a.sort_quantiles, sort_out=a.sort_out)
+    if a.double_sorts:
+        from .sorted_portfolios import parse_double_quantiles
+        kw.update(double_sorts=a.double_sorts, double_quantiles=parse_double_quantiles(a.double_quantiles),
+                  double_mode=a.double_mode, double_out=a.double_out, sort_split=a.sort_split)
+    return kw
+
+
+def main(argv=None):
+    a = _parser().parse_args(argv)
+    kw = _extra_kwargs(a)
     return evaluate_ensemble(a.checkpoint_dirs, a.data_dir, a.device, paper=a.paper_metrics,
                              importance=a.variable_importance, importance_split=a.importance_split,
                              importance_out=a.importance_out, **kw)

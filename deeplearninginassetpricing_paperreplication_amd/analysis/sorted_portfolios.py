@@ -25,8 +25,28 @@ Pricing (``price_portfolios``) uses the project's loading convention (``portfoli
 ``R_i - beta_t w_i``, and the equally weighted portfolio's residual is their mean,
 ``eps[t,p,q] = returns[t,p,q] - beta_t loading[t,p,q]``.
 
+Double sorts (``double_sort_numpy`` is the definition, ``Engine.double_sorted_portfolios`` /
+``csrc/k_qsort2.hip`` the GPU path). For a period with ``n`` valid stocks, a pair of key columns
+``(A, B)`` and ``Qa x Qb`` buckets (``2 <= Qa, Qb <= 16``, ``Qa Qb <= 36``):
+
+* First key: the single sort's rule. With ``s^A`` the ``n`` A-keys ascending,
+  ``bA_d = s^A[ceil(d n / Qa) - 1]`` for ``d = 1..Qa-1`` and ``qa(i) = #{ d : A_i > bA_d }``.
+* Independent mode: the same rule on ``B`` over all ``n`` rows with ``Qb``; one set of
+  breakpoints ``bB_d`` per period, ``qb(i) = #{ d : B_i > bB_d }``.
+* Conditional mode (default, the paper's dependent sort): for each first-key bucket ``a``, with
+  ``S_a = { i : qa(i) = a }`` of ``n_a`` rows and ``s^{B|a}`` their B-keys ascending,
+  ``bB_{a,d} = s^{B|a}[ceil(d n_a / Qb) - 1]`` and ``qb(i) = #{ d : B_i > bB_{qa(i),d} }``.
+  ``n_a = 0`` leaves the cells of row ``a`` empty and its breakpoints NaN, ``n_a < Qb`` leaves
+  some cells empty.
+* Ties share the lowest bucket any of them would get, in both dimensions, so membership never
+  depends on the stock order.
+* Result per (period, pair, cell ``(qa, qb)``): the row count and the float64 sums of the value
+  columns; per (period, pair): ``breaks_a`` [Qa-1] and ``breaks_b`` [Qa][Qb-1] (independent mode:
+  ``Qa`` identical rows). An empty period gives zero counts and sums and NaN breakpoints.
+  ``A == B`` is legal and gets no special case.
+
 Out of scope: value-weighted buckets (the panel carries no market cap; ``sort_buckets_numpy`` and
-the engine method accept further value columns), double sorts, a beta network, plots.
+the engine methods accept further value columns), triple sorts, a beta network, plots.
 """
 from __future__ import annotations
 
@@ -254,6 +274,244 @@ def to_json(res: Dict, priced: Optional[Dict] = None) -> Dict:
     """Plain lists (non-finite values as null): the time means of ``res`` per asset, its counts
     summed over the periods, and every key of ``priced``."""
     out = {"names": list(res["names"]), "quantiles": int(res["quantiles"]),
+           "periods": int(res["count"].shape[0]), "count": _jsonable(res["count"].sum(axis=0))}
+    if priced is not None:
+        out.update({k: _jsonable(v) for k, v in priced.items()})
+    return out
+
+
+# ---------------------------------------------------------------------------------------------
+# Double sorts (definition in the module docstring)
+
+MAX_CELLS = 36
+MAX_DOUBLE_VALUES = 2
+
+
+def _check_q2(quantiles) -> tuple:
+    try:
+        qa, qb = quantiles
+    except (TypeError, ValueError):
+        raise ValueError("quantiles must be a pair (Qa, Qb)") from None
+    Qa, Qb = _check_q(qa), _check_q(qb)
+    if Qa * Qb > MAX_CELLS:
+        raise ValueError(f"Qa * Qb must be at most {MAX_CELLS}")
+    return Qa, Qb
+
+
+def parse_double_quantiles(spec) -> tuple:
+    """CLI form of ``quantiles``: ``"5x5"`` (or a pair, returned checked)."""
+    if isinstance(spec, str):
+        ab = spec.lower().split("x")
+        if len(ab) != 2:
+            raise ValueError(f"double_quantiles: expected QAxQB, got {spec!r}")
+        try:
+            spec = (int(ab[0]), int(ab[1]))
+        except ValueError:
+            raise ValueError(f"double_quantiles: expected QAxQB, got {spec!r}") from None
+    return _check_q2(spec)
+
+
+def _breaks(sorted_keys: np.ndarray, Q: int) -> np.ndarray:
+    n = sorted_keys.shape[0]
+    d = np.arange(1, Q, dtype=np.int64)
+    return sorted_keys[(d * n + Q - 1) // Q - 1]
+
+
+def double_sort_numpy(keys: np.ndarray, pairs: Sequence, mask: np.ndarray, values: np.ndarray,
+                      quantiles=(5, 5), conditional: bool = True) -> Dict:
+    """The definition in numpy. ``keys`` [T][N][P'] (float32 or float64), ``pairs`` a list of
+    (A, B) columns of ``keys``, ``mask`` [T][N], ``values`` [T][N][V]. Returns ``count`` int32
+    [T][P][Qa][Qb], ``sum`` float64 [T][P][Qa][Qb][V], ``breaks_a`` [T][P][Qa-1] and ``breaks_b``
+    [T][P][Qa][Qb-1] in the keys' dtype (NaN where the period, or the first-key bucket, is empty)
+    and ``rows``."""
+    Qa, Qb = _check_q2(quantiles)
+    keys = np.asarray(keys)
+    mask = np.asarray(mask).astype(bool)
+    values = np.asarray(values)
+    T, N, PK = keys.shape
+    V = values.shape[2]
+    pairs = [(int(a), int(b)) for a, b in pairs]
+    for a, b in pairs:
+        if not (0 <= a < PK and 0 <= b < PK):
+            raise ValueError(f"pair ({a}, {b}) outside the {PK} key columns")
+    P = len(pairs)
+    count = np.zeros((T, P, Qa, Qb), np.int32)
+    sums = np.zeros((T, P, Qa, Qb, V), np.float64)
+    breaks_a = np.full((T, P, Qa - 1), np.nan, keys.dtype)
+    breaks_b = np.full((T, P, Qa, Qb - 1), np.nan, keys.dtype)
+    zero = keys.dtype.type(0)
+    for t in range(T):
+        idx = np.nonzero(mask[t])[0]
+        n = int(idx.size)
+        if n == 0:
+            continue
+        v = values[t, idx, :].astype(np.float64)
+        for p, (ca, cb) in enumerate(pairs):
+            kA = keys[t, idx, ca] + zero                      # (-0.0 + 0.0 = +0.0)
+            kB = keys[t, idx, cb] + zero
+            bA = _breaks(np.sort(kA), Qa)
+            qa = (kA[:, None] > bA[None, :]).sum(axis=1)
+            breaks_a[t, p] = bA
+            qb = np.zeros(n, np.int64)
+            if conditional:
+                for a in range(Qa):
+                    sel = qa == a
+                    if not sel.any():
+                        continue
+                    bB = _breaks(np.sort(kB[sel]), Qb)
+                    breaks_b[t, p, a] = bB
+                    qb[sel] = (kB[sel][:, None] > bB[None, :]).sum(axis=1)
+            else:
+                bB = _breaks(np.sort(kB), Qb)
+                breaks_b[t, p, :] = bB[None, :]
+                qb = (kB[:, None] > bB[None, :]).sum(axis=1)
+            cell = qa * Qb + qb
+            onehot = (cell[None, :] == np.arange(Qa * Qb)[:, None]).astype(np.float64)   # [cells][n]
+            count[t, p] = onehot.sum(axis=1).astype(np.int32).reshape(Qa, Qb)
+            sums[t, p] = (onehot @ v).reshape(Qa, Qb, V)
+    return {"count": count, "sum": sums, "breaks_a": breaks_a, "breaks_b": breaks_b, "rows": int(mask.sum())}
+
+
+def _resolve_pairs(pairs: Sequence, F: int, names: Optional[Sequence]) -> List[tuple]:
+    """Pair members as key indices: a column in [0, F), or ``F`` / ``"weight"`` for the ensemble
+    weight (a characteristic's name when ``names`` is given)."""
+    idx = {str(nm): i for i, nm in enumerate(names)} if names is not None and len(names) == F else {}
+
+    def one(m):
+        if isinstance(m, str):
+            if m == "weight":
+                return F
+            if m in idx:
+                return idx[m]
+            try:
+                m = int(m)
+            except ValueError:
+                raise ValueError(f"double sorts: unknown key {m!r}") from None
+        m = int(m)
+        if m < 0 or m > F:
+            raise ValueError(f"double sorts: key {m} outside [0, {F}] ({F} is the weight)")
+        return m
+    out = []
+    for pr in pairs:
+        if len(pr) != 2:
+            raise ValueError(f"double sorts: expected a pair, got {pr!r}")
+        out.append((one(pr[0]), one(pr[1])))
+    return out
+
+
+def _gpu_raw2(spec, batch, w: torch.Tensor, pairs, Qa: int, Qb: int, conditional: bool, precision: str) -> Dict:
+    from ..engine.runner import GANEngine
+    eng = GANEngine(spec, 1, max_epochs=4, precision=precision)
+    eng.set_data(batch)
+    torch.cuda.synchronize(w.device)
+    try:
+        r = eng.eng.double_sorted_portfolios(0, [tuple(p) for p in pairs], Qa, Qb, bool(conditional),
+                                             w.data_ptr(), 1, w.data_ptr(), 1)
+    finally:
+        eng.eng.sync()
+    out = {k: np.asarray(r[k]) for k in ("count", "sum", "breaks_a", "breaks_b")}
+    out["gpu_ms"] = float(r["gpu_ms"])
+    return out
+
+
+def double_sorted_portfolios(models: Sequence, batch: Dict, pairs: Sequence, device: str = "cpu",
+                             quantiles=(5, 5), conditional: bool = True, names: Optional[Sequence] = None,
+                             weights: Optional[np.ndarray] = None, precision: str = "bf16") -> Dict:
+    """Equally weighted ``Qa x Qb`` double-sorted portfolios of ``batch`` for every pair of
+    ``pairs``: members are column indices (or names, with ``names``), or ``F`` / ``"weight"`` for
+    the ensemble weight (on the GPU the weight is the engine method's one extra key).
+
+    Returns ``returns`` and ``loading`` [T][P][Qa][Qb] (cell mean return / ensemble weight, NaN
+    where the cell is empty), ``count`` int32 [T][P][Qa][Qb], ``breaks_a`` [T][P][Qa-1],
+    ``breaks_b`` [T][P][Qa][Qb-1], ``pairs`` (resolved indices), ``names`` (``"A x B"``),
+    ``quantiles`` (Qa, Qb), ``mode`` and, on the GPU, ``gpu_ms``. ``weights`` and ``precision`` as
+    for ``sorted_portfolios``."""
+    Qa, Qb = _check_q2(quantiles)
+    models = list(models)
+    mask = batch["mask"].bool()
+    T, N, F = batch["individual_features"].shape
+    prs = _resolve_pairs(pairs, F, names)
+    gpu = str(device).startswith("cuda")
+    if gpu:
+        from ..ops import native
+        if native.load(required=False) is None:
+            print("[sorted_portfolios] native extension not available: using the CPU path")
+            gpu = False
+    if not models and (weights is None or gpu):      # (the engine is built from a model's spec)
+        raise ValueError("no models")
+    if gpu:
+        dev = torch.device("cuda", torch.cuda.current_device())
+        if weights is None:
+            w = _gpu_weights(models, batch)
+        else:
+            w = torch.as_tensor(np.asarray(weights, dtype=np.float32)).to(dev).contiguous()
+        raw = _gpu_raw2(models[0].spec, batch, w, prs, Qa, Qb, conditional, precision)
+    else:
+        cpu = {k: (v.cpu() if isinstance(v, torch.Tensor) else v) for k, v in batch.items()}
+        w = _cpu_weights(models, cpu) if weights is None else np.asarray(weights)
+        w = w.astype(np.float32)
+        keys = np.concatenate([cpu["individual_features"].numpy().astype(np.float32), w[:, :, None]], axis=2)
+        vals = np.stack([cpu["returns"].numpy().astype(np.float32), w], axis=2)
+        raw = double_sort_numpy(keys, prs, mask.cpu().numpy(), vals, (Qa, Qb), conditional)
+    cnt = raw["count"]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        mean = np.where(cnt[..., None] > 0, raw["sum"] / cnt[..., None], np.nan)
+    kn = _key_names(F, True, names)
+    out = {"returns": mean[..., 0], "loading": mean[..., 1], "count": cnt, "breaks_a": raw["breaks_a"],
+           "breaks_b": raw["breaks_b"], "pairs": prs, "names": [f"{kn[a]} x {kn[b]}" for a, b in prs],
+           "quantiles": (Qa, Qb), "mode": "conditional" if conditional else "independent"}
+    if "gpu_ms" in raw:
+        out["gpu_ms"] = raw["gpu_ms"]
+    return out
+
+
+def price_double_sorted(res: Dict, weights: np.ndarray, returns: np.ndarray, mask: np.ndarray) -> Dict:
+    """Price the ``P * Qa * Qb`` test assets of ``res`` (``double_sorted_portfolios``) with the SDF
+    weight ``weights`` [T][N]: the cells are flattened to [T][P][Qa Qb] and priced by
+    ``price_portfolios``.
+
+    Per asset ([P][Qa][Qb]): ``mean_ret``, ``alpha``, ``t_alpha``, ``ev_asset``. Per pair ([P], over
+    the pair's non-empty cells, the formulas of ``price_portfolios``' overall numbers; the paper's
+    per-table figures): ``pair_ev``, ``pair_xs_r2``, ``pair_mean_abs_alpha``, and the corner spread
+    cell(Qa-1, Qb-1) - cell(0, 0) over the periods where both exist, ``hml`` with its Sharpe ratio
+    ``hml_sharpe``. Over all pairs: ``ev``, ``xs_r2``, ``mean_abs_alpha``, ``assets``."""
+    cnt = np.asarray(res["count"])
+    T, P, Qa, Qb = cnt.shape
+
+    def flat(sel):
+        return {"names": list(res["names"])[sel],
+                **{k: np.asarray(res[k])[:, sel].reshape(T, -1, Qa * Qb) for k in ("count", "returns", "loading")}}
+    allp = price_portfolios(flat(slice(None)), weights, returns, mask)
+    out = {k: allp[k].reshape(P, Qa, Qb) for k in ("mean_ret", "alpha", "t_alpha", "ev_asset")}
+    per = [price_portfolios(flat(slice(p, p + 1)), weights, returns, mask) for p in range(P)]
+    out.update({"pair_ev": np.array([q["ev"] for q in per], np.float64),
+                "pair_xs_r2": np.array([q["xs_r2"] for q in per], np.float64),
+                "pair_mean_abs_alpha": np.array([q["mean_abs_alpha"] for q in per], np.float64),
+                "hml": allp["hml"], "hml_sharpe": allp["hml_sharpe"], "ev": allp["ev"], "xs_r2": allp["xs_r2"],
+                "mean_abs_alpha": allp["mean_abs_alpha"], "assets": allp["assets"], "names": list(res["names"]),
+                "quantiles": tuple(res["quantiles"]), "mode": res["mode"]})
+    return out
+
+
+def format_double_sorted(priced: Dict) -> List[str]:
+    """The printed report: the overall line, then per pair its EV / XS-R2 / mean |alpha|, the corner
+    spread with its Sharpe ratio, and the Qa x Qb table of cell mean returns (rows: first key)."""
+    P, Qa, Qb = priced["mean_ret"].shape
+    lines = [f"  {priced['assets']} test assets ({P} pairs x {Qa} x {Qb} cells, {priced['mode']}):  "
+             f"EV {priced['ev']:7.4f}  XS-R2 {priced['xs_r2']:7.4f}  mean |alpha| {priced['mean_abs_alpha']:.3e}"]
+    for p, name in enumerate(priced["names"]):
+        lines.append(f"  {name}:  EV {priced['pair_ev'][p]:7.4f}  XS-R2 {priced['pair_xs_r2'][p]:7.4f}  "
+                     f"mean |alpha| {priced['pair_mean_abs_alpha'][p]:.3e}  corner H-L {priced['hml'][p]: .4f}  "
+                     f"SR {priced['hml_sharpe'][p]: .3f}")
+        lines += ["    " + " ".join(f"{v: .4f}" for v in row) for row in priced["mean_ret"][p]]
+    return lines
+
+
+def double_to_json(res: Dict, priced: Optional[Dict] = None) -> Dict:
+    """Plain lists (non-finite values as null): the counts of ``res`` summed over the periods and
+    every key of ``priced``."""
+    out = {"names": list(res["names"]), "pairs": [list(p) for p in res["pairs"]],
+           "quantiles": [int(q) for q in res["quantiles"]], "mode": res["mode"],
            "periods": int(res["count"].shape[0]), "count": _jsonable(res["count"].sum(axis=0))}
     if priced is not None:
         out.update({k: _jsonable(v) for k, v in priced.items()})
