@@ -43,6 +43,7 @@
 #include "panel.h"
 #include "qsort.h"
 #include "qsort2.h"
+#include "linport.h"
 #include "rnn.h"
 #include "update.h"
 #include "wide.h"
@@ -1004,6 +1005,133 @@ class Engine {
     }
     py::dict d;
     d["count"] = cnt; d["sum"] = sum; d["breaks_a"] = bra; d["breaks_b"] = brb; d["rows"] = D.R; d["gpu_ms"] = ms;
+    return d;
+  }
+  // Linear benchmark SDFs of split s (k_linport.hip, definitions in linport.h and
+  // analysis/benchmarks.py). Both methods read the panel only -- no model, job table or graph -- and
+  // cut every period into segments of LINPORT_SEG rows; fp64 sums in a fixed order, so repeated
+  // calls are bitwise identical. An empty split returns zeros and launches nothing.
+  //
+  // The segment table of the split: (period, first row within it) per segment and the periods'
+  // segment ranges, from the host copy of row_ptr. Returns the number of segments.
+  int lin_segments(const SplitDev& D, DevBuf<int>& dseg, DevBuf<int>& dsegptr) {
+    std::vector<int> rp((size_t)D.T + 1), seg, sp((size_t)D.T + 1, 0);
+    HIP_LEGACY(hipMemcpy(rp.data(), D.row_ptr.p, rp.size() * sizeof(int), hipMemcpyDeviceToHost));
+    for (int t = 0; t < D.T; ++t) {
+      for (int off = 0; off < rp[t + 1] - rp[t]; off += LINPORT_SEG) { seg.push_back(t); seg.push_back(off); }
+      sp[t + 1] = (int)(seg.size() / 2);
+    }
+    up(dseg, seg.data(), seg.size());
+    up(dsegptr, sp.data(), sp.size());
+    return (int)(seg.size() / 2);
+  }
+  void lin_panel_args(const SplitDev& D, LinportArgs& A) {
+    A.X = D.X.p; A.KP = md_.KP; A.fp32 = md_.md.fp32 ? 1 : 0; A.F = md_.F;
+    A.Rc = D.Rc.p; A.rowti = reinterpret_cast<const int2*>(D.rowti.p); A.row_ptr = D.row_ptr.p;
+    A.T = D.T; A.N = D.N;
+  }
+  bool linear_supported() const { return linport_supported(md_.F); }
+  // managed_portfolios: sum_x, sum_xr fp64 [T][F] (sum_i x and sum_i x R over the valid rows of each
+  // period, x as the engine stores it), n int32 [T], rows (= R) and gpu_ms.
+  py::dict managed_portfolios(int s) {
+    if (s < 0 || s > 2) throw std::invalid_argument("split must be 0, 1 or 2");
+    const SplitDev& D = splits_[s];
+    if (!D.set) throw std::runtime_error("split not set");
+    if (D.T > 65535) throw std::invalid_argument("managed_portfolios: more than 65535 periods");
+    const int F = md_.F;
+    py::array_t<double> sx({D.T, F}), sxr({D.T, F});
+    py::array_t<int> nn(D.T);
+    std::fill_n(sx.mutable_data(), sx.size(), 0.0);
+    std::fill_n(sxr.mutable_data(), sxr.size(), 0.0);
+    std::fill_n(nn.mutable_data(), nn.size(), 0);
+    float ms = 0.f;
+    if (D.R > 0 && D.T > 0) {
+      DevBuf<int> dseg, dsp, dn;
+      DevBuf<double> part, out;
+      LinportArgs A{};
+      lin_panel_args(D, A);
+      A.nseg = lin_segments(D, dseg, dsp);
+      A.seg = reinterpret_cast<const int2*>(dseg.p); A.seg_ptr = dsp.p;
+      part.alloc((size_t)A.nseg * 2 * F, false); out.alloc((size_t)2 * D.T * F, false); dn.alloc(D.T, false);
+      A.part = part.p; A.out = out.p; A.n = dn.p;
+      hipEvent_t ev[2];
+      for (auto& e : ev) HIP_OK(hipEventCreate(&e));
+      HIP_OK(hipEventRecord(ev[0], st_));
+      launch_managed(A, st_);
+      HIP_OK(hipEventRecord(ev[1], st_));
+      sync();
+      HIP_OK(hipEventElapsedTime(&ms, ev[0], ev[1]));
+      for (auto& e : ev) HIP_OK(hipEventDestroy(e));
+      HIP_LEGACY(hipMemcpy(sx.mutable_data(), out.p, sx.size() * sizeof(double), hipMemcpyDeviceToHost));
+      HIP_LEGACY(hipMemcpy(sxr.mutable_data(), out.p + sx.size(), sxr.size() * sizeof(double), hipMemcpyDeviceToHost));
+      HIP_LEGACY(hipMemcpy(nn.mutable_data(), dn.p, nn.size() * sizeof(int), hipMemcpyDeviceToHost));
+    }
+    py::dict d;
+    d["sum_x"] = sx; d["sum_xr"] = sxr; d["n"] = nn; d["rows"] = D.R; d["gpu_ms"] = ms;
+    return d;
+  }
+  // linear_portfolios: theta float32 [K][F] (1 <= K <= 64), center float32 [T][K] or None (zeros),
+  // w_out a dense device buffer [K][T][N] fp32 or 0: v = fp32(x . theta_k - center[t][k]) is written
+  // at the valid (t, i) on the engine stream, every other element is left as it is. Returns s1, sa,
+  // s2, sr fp64 [T][K], n int32 [T], sum_r, sum_rr fp64 [T], rows and gpu_ms.
+  py::dict linear_portfolios(int s, py::array_t<float, py::array::c_style | py::array::forcecast> theta,
+                             py::object center, uintptr_t w_out) {
+    if (s < 0 || s > 2) throw std::invalid_argument("split must be 0, 1 or 2");
+    if (theta.ndim() != 2 || theta.shape(1) != md_.F) throw std::invalid_argument("linear_portfolios: theta must be [K][F]");
+    const int K = (int)theta.shape(0), F = md_.F;
+    if (K < 1 || K > LINPORT_MAX_K) throw std::invalid_argument("linear_portfolios: K must be in [1, 64]");
+    if (!linport_supported(F))
+      throw std::invalid_argument("linear_portfolios: not available for this shape (theta exceeds the LDS budget)");
+    const SplitDev& D = splits_[s];
+    if (!D.set) throw std::runtime_error("split not set");
+    if (D.T > 65535) throw std::invalid_argument("linear_portfolios: more than 65535 periods");
+    py::array_t<float, py::array::c_style | py::array::forcecast> cen;
+    const bool has_c = !center.is_none();
+    if (has_c) {
+      cen = py::array_t<float, py::array::c_style | py::array::forcecast>::ensure(center);
+      if (!cen || cen.ndim() != 2 || cen.shape(0) != D.T || cen.shape(1) != K)
+        throw std::invalid_argument("linear_portfolios: center must be [T][K]");
+    }
+    py::array_t<double> r1({D.T, K}), ra({D.T, K}), r2({D.T, K}), rr({D.T, K}), sr(D.T), srr(D.T);
+    py::array_t<int> nn(D.T);
+    for (auto* a : {&r1, &ra, &r2, &rr, &sr, &srr}) std::fill_n(a->mutable_data(), a->size(), 0.0);
+    std::fill_n(nn.mutable_data(), nn.size(), 0);
+    float ms = 0.f;
+    if (D.R > 0 && D.T > 0) {
+      DevBuf<int> dseg, dsp, dn;
+      DevBuf<double> part, partr, out, outr;
+      DevBuf<float> dth, dc;
+      std::vector<float> packed(linport_theta_floats(F, K));
+      linport_pack_theta(theta.data(), K, F, packed.data());
+      up(dth, packed.data(), packed.size());
+      if (has_c) up(dc, cen.data(), (size_t)cen.size());
+      LinportArgs A{};
+      lin_panel_args(D, A);
+      A.nseg = lin_segments(D, dseg, dsp);
+      A.seg = reinterpret_cast<const int2*>(dseg.p); A.seg_ptr = dsp.p;
+      A.K = K; A.theta = dth.p; A.center = has_c ? dc.p : nullptr; A.w_out = reinterpret_cast<float*>(w_out);
+      const size_t TK = (size_t)D.T * K;
+      part.alloc(linport_part_doubles(A.nseg, K), false); partr.alloc((size_t)A.nseg * 2, false);
+      out.alloc(4 * TK, false); outr.alloc((size_t)2 * D.T, false); dn.alloc(D.T, false);
+      A.part = part.p; A.part_r = partr.p; A.out = out.p; A.out_r = outr.p; A.n = dn.p;
+      hipEvent_t ev[2];
+      for (auto& e : ev) HIP_OK(hipEventCreate(&e));
+      HIP_OK(hipEventRecord(ev[0], st_));
+      launch_linport(A, st_);
+      HIP_OK(hipEventRecord(ev[1], st_));
+      sync();
+      HIP_OK(hipEventElapsedTime(&ms, ev[0], ev[1]));
+      for (auto& e : ev) HIP_OK(hipEventDestroy(e));
+      int j = 0;
+      for (auto* a : {&r1, &ra, &r2, &rr})
+        HIP_LEGACY(hipMemcpy(a->mutable_data(), out.p + TK * j++, TK * sizeof(double), hipMemcpyDeviceToHost));
+      HIP_LEGACY(hipMemcpy(sr.mutable_data(), outr.p, D.T * sizeof(double), hipMemcpyDeviceToHost));
+      HIP_LEGACY(hipMemcpy(srr.mutable_data(), outr.p + D.T, D.T * sizeof(double), hipMemcpyDeviceToHost));
+      HIP_LEGACY(hipMemcpy(nn.mutable_data(), dn.p, nn.size() * sizeof(int), hipMemcpyDeviceToHost));
+    }
+    py::dict d;
+    d["s1"] = r1; d["sa"] = ra; d["s2"] = r2; d["sr"] = rr; d["n"] = nn; d["sum_r"] = sr; d["sum_rr"] = srr;
+    d["rows"] = D.R; d["gpu_ms"] = ms;
     return d;
   }
   // SDF weight structure of split s (k_wsurf.hip, definition in wsurf.h): the raw weight of the
@@ -2807,6 +2935,10 @@ PYBIND11_MODULE(_dlap_hip, m) {
       .def("double_sorted_portfolios", &Engine::double_sorted_portfolios, py::arg("s"), py::arg("pairs"),
            py::arg("qa") = 5, py::arg("qb") = 5, py::arg("conditional") = true, py::arg("extra_keys") = 0,
            py::arg("n_extra") = 0, py::arg("values") = 0, py::arg("n_values") = 0)
+      .def("managed_portfolios", &Engine::managed_portfolios, py::arg("s"))
+      .def("linear_portfolios", &Engine::linear_portfolios, py::arg("s"), py::arg("theta"),
+           py::arg("center") = py::none(), py::arg("w_out") = 0)
+      .def("linear_supported", &Engine::linear_supported)
       .def("weight_surface", &Engine::weight_surface, py::arg("s"), py::arg("scale"), py::arg("grid"), py::arg("base"),
            py::arg("items"), py::arg("refresh") = true)
       .def("weight_surface_supported", [](Engine& e, int s) { return e.wsurf_ok(s); }, py::arg("s") = 0)

@@ -93,7 +93,9 @@ def evaluate_ensemble(checkpoint_dirs: Sequence[str], data_dir: str, device: str
                       sort_split: str = "test", sort_quantiles: int = 10, sort_out: str = None,
                       weight_structure: bool = False, structure_split: str = "test", structure_points: int = 21,
                       structure_pairs=None, structure_out: str = None, double_sorts=None,
-                      double_quantiles=(5, 5), double_mode: str = "conditional", double_out: str = None) -> Dict:
+                      double_quantiles=(5, 5), double_mode: str = "conditional", double_out: str = None,
+                      benchmarks: bool = False, benchmark_grid=(16, 4), benchmark_center: str = "mean",
+                      benchmarks_out: str = None) -> Dict:
     """Reference output and return value; ``paper=True`` (CLI ``--paper_metrics``) adds the
     paper's EV / XS-R² / turnover / max 1-month loss of the ensemble's SDF factor per split;
     ``importance=True`` (CLI ``--variable_importance``) adds the sensitivity ranking of the
@@ -114,7 +116,11 @@ def evaluate_ensemble(checkpoint_dirs: Sequence[str], data_dir: str, device: str
     name, column or ``weight``) adds the ``double_quantiles`` = (Qa, Qb) double-sorted portfolios
     of ``sort_split`` (``double_mode``: ``conditional`` or ``independent``), priced by the SDF
     (``analysis.sorted_portfolios.double_sorted_portfolios``), under the key ``double_sorts`` and
-    writes them to ``double_out`` (JSON) when given."""
+    writes them to ``double_out`` (JSON) when given;
+    ``benchmarks=True`` (CLI ``--benchmarks``) adds the linear (LS) and elastic-net (EN) benchmark
+    SDFs (``analysis.benchmarks``: EN over the ``benchmark_grid`` = (n1, n2) penalties, selected on
+    the validation split; ``benchmark_center``: ``mean`` or ``none``) next to the ensemble in one
+    table, under the key ``benchmarks``, and writes them to ``benchmarks_out`` (JSON) when given."""
     say = print if verbose else (lambda *a, **k: None)
     bar = "=" * 70
     say(bar); say(f"ENSEMBLE EVALUATION ({len(checkpoint_dirs)} models, averaged weights)"); say(bar); say()
@@ -242,6 +248,27 @@ def evaluate_ensemble(checkpoint_dirs: Sequence[str], data_dir: str, device: str
             with open(double_out, "w") as fh:
                 json.dump(sp.double_to_json(res_ds, priced), fh, indent=1)
             say(f"  Saved: {double_out}"); say()
+    if benchmarks:
+        from . import benchmarks as bm
+        from .portfolio import cross_sectional_r2, explained_variation
+        res_bm = bm.linear_benchmarks(batches, device=device, center=benchmark_center, grid=bm.parse_grid(benchmark_grid))
+        tb = np_batches["test"]
+        if str(device).startswith("cuda"):
+            wavg = average_weights(list(wdev["test"].cpu().numpy()), tb["mask"])
+        else:
+            wavg = average_weights([w["test"] for w in weights], tb["mask"])
+        gan = {"train_sharpe": res["train_sharpe"], "valid_sharpe": res["valid_sharpe"], "test_sharpe": res["test_sharpe"],
+               "ev": explained_variation(wavg, tb["returns"], tb["mask"]),
+               "xs_r2": cross_sectional_r2(wavg, tb["returns"], tb["mask"])}
+        out["benchmarks"] = {"linear": res_bm, "gan": gan}
+        say(bar); say("BENCHMARK SDFS (linear LS / elastic net EN vs the ensemble)"); say(bar); say()
+        for line in bm.format_benchmarks(res_bm, gan):
+            say(line)
+        say()
+        if benchmarks_out:
+            with open(benchmarks_out, "w") as fh:
+                json.dump(bm.to_json(res_bm, gan), fh, indent=1)
+            say(f"  Saved: {benchmarks_out}"); say()
     if weight_structure:
         from . import weight_structure as wst
         if structure_split not in SPLITS:
@@ -292,6 +319,11 @@ def _parser():
     p.add_argument("--double_quantiles", type=str, default="5x5", help="QAxQB buckets (2..16 each, at most 36 cells)")
     p.add_argument("--double_mode", type=str, default="conditional", choices=("conditional", "independent"))
     p.add_argument("--double_out", type=str, default=None, help="write the double-sorted results to FILE.json")
+    p.add_argument("--benchmarks", action="store_true",
+                   help="also evaluate the linear (LS) and elastic-net (EN) benchmark SDFs next to the ensemble")
+    p.add_argument("--benchmark_grid", type=str, default="16x4", help="EN penalties: N1xN2 values of l1 x l2 (N2 <= 4)")
+    p.add_argument("--benchmark_center", type=str, default="mean", choices=("mean", "none"))
+    p.add_argument("--benchmarks_out", type=str, default=None, help="write the benchmark results to FILE.json")
     return p
 
 
@@ -307,6 +339,10 @@ def _extra_kwargs(a) -> Dict:
         from .sorted_portfolios import parse_double_quantiles
         kw.update(double_sorts=a.double_sorts, double_quantiles=parse_double_quantiles(a.double_quantiles),
                   double_mode=a.double_mode, double_out=a.double_out, sort_split=a.sort_split)
+    if a.benchmarks:
+        from .benchmarks import parse_grid
+        kw.update(benchmarks=True, benchmark_grid=parse_grid(a.benchmark_grid), benchmark_center=a.benchmark_center,
+                  benchmarks_out=a.benchmarks_out)
     return kw
 
 
