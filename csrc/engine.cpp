@@ -44,6 +44,7 @@
 #include "qsort.h"
 #include "qsort2.h"
 #include "linport.h"
+#include "pred.h"
 #include "rnn.h"
 #include "update.h"
 #include "wide.h"
@@ -1134,6 +1135,149 @@ class Engine {
     d["rows"] = D.R; d["gpu_ms"] = ms;
     return d;
   }
+  // ---- prediction towers (k_pred.hip, definitions in pred.h and analysis/prediction.py) ----
+  // The SDF tower (LSTM state + characteristics -> one scalar per row) fitted by mean squared
+  // error to y[t, i] = R[t, i] f[t]: the FFN return-prediction benchmark (f = 1) and the beta
+  // network (f = the SDF factor). The loss and its gradient come from k_pred_loss, the backward
+  // from the pieces xs_backward runs, the update from k_adam, the bookkeeping from k_pred_end;
+  // the moment network of the model rides along unused (no moments, no Gram build, one stream).
+  //
+  // pred_loss: the loss of split s on what the evaluation forward leaves in W.w (refresh: run it
+  // first; false: whatever forward_split left there). Returns n int32 [T], sums fp64 [G][6][T]
+  // (SE, SY, S1, SA, S2, SR), loss fp64 [G]. write_dw (train split): also fills W.dw. An empty
+  // split returns zeros and launches nothing.
+  py::dict pred_loss(int s, py::object factor, const std::string& weighting, bool refresh = true,
+                     bool write_dw = false) {
+    if (s < 0 || s > 2) throw std::invalid_argument("split must be 0, 1 or 2");
+    if (write_dw && s != 0) throw std::invalid_argument("pred_loss: dw exists for the train split only");
+    ensure_jobs();
+    const SplitDev& D = splits_[s];
+    if (!D.set) throw std::runtime_error("split not set");
+    const int wt = pred_weighting(weighting);
+    sync();
+    fit_ready_ = false;                       // (the split's tables are rebuilt: a fit begins again)
+    pred_prepare(s, factor, wt);
+    pred_alloc_models();
+    pred_build_end();
+    py::array_t<int> nn(D.T);
+    py::array_t<double> sums({G_, (int)PRED_NSUM, D.T}), loss(G_);
+    std::copy(fit_[s].n.begin(), fit_[s].n.end(), nn.mutable_data());
+    std::fill_n(sums.mutable_data(), sums.size(), 0.0);
+    std::fill_n(loss.mutable_data(), loss.size(), 0.0);
+    if (D.R > 0 && D.T > 0) {
+      if (refresh) fwd_only(s, false, false, false);
+      PredArgs A = pred_args(s);
+      A.write_dw = write_dw ? 1 : 0;
+      launch_pred_loss(A, G_, st_);
+      launch_pred_end(as<PredEndJob>(j_pred_end_), G_, 1 << s, 0, md_.P, st_);
+      sync();
+      const size_t per = (size_t)PRED_NSUM * D.T;
+      for (int g = 0; g < G_; ++g) {
+        HIP_LEGACY(hipMemcpy(sums.mutable_data() + (size_t)g * per, fitm_[g].sums[s].p, per * sizeof(double),
+                             hipMemcpyDeviceToHost));
+        HIP_LEGACY(hipMemcpy(loss.mutable_data() + g, fitm_[g].loss.p + s, sizeof(double), hipMemcpyDeviceToHost));
+      }
+    }
+    py::dict d;
+    d["n"] = nn; d["sums"] = sums; d["loss"] = loss; d["rows"] = D.R;
+    return d;
+  }
+  // fit_begin: factors holds, per split, a host fp32 array [T_s] or None (ones). Uploads them,
+  // builds the job tables and zeroes the history, the best tracker and the fit epoch counter.
+  void fit_begin(std::vector<py::object> factors, const std::string& weighting) {
+    if (xs_on_) throw std::runtime_error("fit_begin: not available on a sharded engine");
+    if (ext_stream_) throw std::runtime_error("fit_begin needs the engine's own stream (set_stream(0, False))");
+    if (!splits_[0].set) throw std::runtime_error("train split not set");
+    if (factors.size() != 3) throw std::invalid_argument("fit_begin: factors must hold one entry per split");
+    const int wt = pred_weighting(weighting);
+    ensure_jobs();
+    sync();
+    fit_mask_ = 0;
+    for (int s = 0; s < 3; ++s) {
+      if (!splits_[s].set) continue;
+      pred_prepare(s, factors[s], wt);
+      fit_mask_ |= 1 << s;
+      if (s > 0) fwd_tab(s, false, false);    // (built here: fit_epochs issues no allocation or synchronous copy)
+    }
+    pred_alloc_models();
+    pred_build_end();
+    for (FitModel& M : fitm_) HIP_OK(hipMemsetAsync(M.hist.p, 0, M.hist.n * sizeof(float), st_));
+    launch_pred_begin(as<PredEndJob>(j_pred_end_), G_, st_);
+    fit_ready_ = true;
+  }
+  // fit_epochs: n epochs on the engine stream, no host synchronisation between them. An epoch is
+  // the train forward (as xs_backward runs it), k_pred_loss (writes W.dw), the tower backward, the
+  // backward tail, clip + Adam, the evaluation-mode towers and k_pred_loss of each evaluation
+  // split, and k_pred_end: the validation loss of epoch e is that of the parameters after update e.
+  void fit_epochs(int n, float lr) {
+    install_crash_handler();
+    if (!fit_ready_ || graphs_dirty_) throw std::runtime_error("fit_epochs: call fit_begin first (and after any change of the splits or models)");
+    if (xs_on_ || ext_stream_) throw std::runtime_error("fit_epochs needs the engine's own stream and no sharding");
+    TrainPass tp(1);
+    tp.own_proj = false;                      // (k_proj projects the recurrence's inputs and rearms the progress counter)
+    PredArgs A0 = pred_args(0);
+    A0.write_dw = 1;
+    for (int e = 0; e < n; ++e) {
+      enqueue_train_fwd(tp);
+      launch_pred_loss(A0, G_, st_);
+      launch_sdf_bwd(as<MlpJob>(j_mlp_bwd_[1]));
+      if (md_.md.wide)
+        launch_wgrad0(as<WideJob>(j_wide_bwd_[1]), G_, dd(), md_.md, false, md_.WMB, nsplit_, st_);
+      enqueue_train_tail(tp);
+      enqueue_update(1, lr);
+      for (int s = 1; s < 3; ++s) {
+        if (!((fit_mask_ >> s) & 1)) continue;
+        if (splits_[s].R > 0 && splits_[s].T > 0) enqueue_fwd_towers(fwd_tab(s, false, false), s, false, false);
+        launch_pred_loss(pred_args(s), G_, st_);
+      }
+      launch_pred_end(as<PredEndJob>(j_pred_end_), G_, fit_mask_, 1, md_.P, st_);
+    }
+  }
+  // history rows [epochs][PRED_HIST_W] (train, valid, test loss, gradient norm, is_best) of model g
+  py::array_t<float> fit_history(int g) {
+    check_g(g);
+    if (fitm_.empty()) throw std::runtime_error("fit_history: no fit has run");
+    sync();
+    int ep[2];
+    HIP_LEGACY(hipMemcpy(ep, fitm_[g].ep.p, sizeof(ep), hipMemcpyDeviceToHost));
+    const int n = std::min(ep[0], max_epochs_);
+    py::array_t<float> out({n, (int)PRED_HIST_W});
+    if (n) HIP_LEGACY(hipMemcpy(out.mutable_data(), fitm_[g].hist.p, (size_t)n * PRED_HIST_W * sizeof(float), hipMemcpyDeviceToHost));
+    return out;
+  }
+  // (best epoch, its validation loss) of model g; (-1, inf) when no epoch has improved
+  py::tuple fit_best(int g) {
+    check_g(g);
+    if (fitm_.empty()) throw std::runtime_error("fit_best: no fit has run");
+    sync();
+    int ep[2];
+    float best;
+    HIP_LEGACY(hipMemcpy(ep, fitm_[g].ep.p, sizeof(ep), hipMemcpyDeviceToHost));
+    HIP_LEGACY(hipMemcpy(&best, fitm_[g].best.p, sizeof(best), hipMemcpyDeviceToHost));
+    return py::make_tuple(ep[1], best);
+  }
+  // the best-epoch snapshot of every model that took one becomes its parameters (re-packed)
+  void fit_load_best() {
+    if (fitm_.empty()) throw std::runtime_error("fit_load_best: no fit has run");
+    sync();
+    for (int g = 0; g < G_; ++g) {
+      int ep[2];
+      HIP_LEGACY(hipMemcpy(ep, fitm_[g].ep.p, sizeof(ep), hipMemcpyDeviceToHost));
+      if (ep[1] < 0) continue;
+      HIP_OK(hipMemcpyAsync(models_[g].params.p, fitm_[g].snap.p, md_.P * sizeof(float), hipMemcpyDeviceToDevice, st_));
+      pack(g, false);
+    }
+    sync();
+    h_valid_ = false;
+  }
+  // clip + Adam of `phase` on the gradients the last backward left (tests: the last step of a
+  // hand-driven epoch)
+  void apply_update(int phase, float lr) {
+    check_phase(phase);
+    ensure_jobs();
+    enqueue_update(phase, lr);
+  }
+
   // SDF weight structure of split s (k_wsurf.hip, definition in wsurf.h): the raw weight of the
   // base row with the characteristics of each item moved over the grid, summed over the split's
   // periods and the models with the factors `scale` (device fp32 [G][T], 0: ones; read on the
@@ -2272,6 +2416,7 @@ class Engine {
     for (auto& kv : graphs_) retire_graph_exec(kv.second, st_);
     graphs_.clear();
     fwd_tables_.clear();
+    fit_ready_ = false;
     j_mlp_bwd_dh_.free();
     {   // backward launch shape over the fixed fine-slab partition: one workgroup per fine slab
         // (the compile-time one-slab kernel). DLAP_BWD_FPW=4 walks four fine slabs per
@@ -2791,13 +2936,10 @@ class Engine {
     capture_s_ += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_cap).count();
     return exec;
   }
-  void fwd_only(int s, bool train_mode, bool do_mom, bool wait) {
-    const SplitDev& D = splits_[s];
-    if (!D.set) throw std::runtime_error("split not set");
-    join_eval_gram();
-    // job tables of (split, mode) for every model, built once per rebuild (module API calls
-    // issue no host allocation / synchronous copy). The train split keeps its LSTM state
-    // (final (h, c) of every layer for the module API).
+  // job tables of (split, mode) for every model, built once per rebuild (module API calls
+  // issue no host allocation / synchronous copy). The train split keeps its LSTM state
+  // (final (h, c) of every layer for the module API).
+  FwdTables& fwd_tab(int s, bool train_mode, bool do_mom) {
     const int key = s * 4 + (train_mode ? 2 : 0) + (do_mom ? 1 : 0);
     FwdTables& F = fwd_tables_[key];
     if (!F.built) {
@@ -2815,20 +2957,136 @@ class Engine {
       upload(F.r, rj); upload(F.m, mj); upload(F.l, lj); upload(F.w, wj);
       F.built = true;
     }
-    DevBuf<char>& a = F.r;
-    DevBuf<char>& b = F.m;
-    DevBuf<char>& c = F.l;
-    DevBuf<char>& w = F.w;
+    return F;
+  }
+  // the LSTM prologue and the towers of split s (layer 0 through k_proj0 or inside the towers on
+  // the wide path): W.w (and the moments) of every model, no loss pass
+  void enqueue_fwd_towers(FwdTables& F, int s, bool train_mode, bool do_mom) {
+    const SplitDev& D = splits_[s];
     const bool zx = md_.md.wide && k_.zx_eval && !train_mode;
-    if (md_.md.wide && !zx) launch_proj0(as<WideJob>(w), G_, gx_proj_[s], md_.md, md_.WMB, st_);
-    launch_prologue(as<RnnJob>(a), G_, D.T, dd(), md_, st_, do_mom);
-    if (zx) launch_mlp_fwd_zx(as<MlpJob>(b), G_, std::max(1, k_.zx_gx / G_), md_.md, md_.WMB, st_);
-    else launch_mlp_fwd(as<MlpJob>(b), G_, gx_fwd_[s], md_.md, md_.KS1, md_.WMB, st_);
+    if (md_.md.wide && !zx) launch_proj0(as<WideJob>(F.w), G_, gx_proj_[s], md_.md, md_.WMB, st_);
+    launch_prologue(as<RnnJob>(F.r), G_, D.T, dd(), md_, st_, do_mom);
+    if (zx) launch_mlp_fwd_zx(as<MlpJob>(F.m), G_, std::max(1, k_.zx_gx / G_), md_.md, md_.WMB, st_);
+    else launch_mlp_fwd(as<MlpJob>(F.m), G_, gx_fwd_[s], md_.md, md_.KS1, md_.WMB, st_);
+  }
+  void fwd_only(int s, bool train_mode, bool do_mom, bool wait) {
+    const SplitDev& D = splits_[s];
+    if (!D.set) throw std::runtime_error("split not set");
+    join_eval_gram();
+    FwdTables& F = fwd_tab(s, train_mode, do_mom);
+    DevBuf<char>& c = F.l;
+    enqueue_fwd_towers(F, s, train_mode, do_mom);
     period_fwd(as<LossJob>(c), G_, D.T, st_, true, 1 << s);
     launch_asset(as<LossJob>(c), G_, D.N, md_.K, st_);
     if (xs_on_) { launch_xs_loss_sums(as<LossJob>(c), G_, st_); xs_call("loss", 1 << s, st_); }
     launch_job_metrics(as<LossJob>(c), G_, st_);
     if (wait) sync();
+  }
+
+  // ---- prediction towers (pred_loss / fit_*): per-split tables and per-model buffers ----------
+  struct FitSplit {
+    DevBuf<int> seg, seg_ptr;                // the split's segment table (lin_segments)
+    DevBuf<float> c, f;                      // [T] row weights, [T] factor (has_f)
+    DevBuf<char> jobs;                       // PredJob per model
+    std::vector<int> n;                      // rows per period (host copy)
+    int nseg = 0;
+    bool has_f = false, ready = false;
+  };
+  struct FitModel {
+    DevBuf<double> part[3], sums[3], loss;
+    DevBuf<float> hist, best, snap;
+    DevBuf<int> ep;
+  };
+  FitSplit fit_[3];
+  std::vector<FitModel> fitm_;
+  DevBuf<char> j_pred_end_;
+  bool fit_ready_ = false;                   // fit_begin's tables match the current job tables
+  int fit_mask_ = 0;                         // the splits of the fit (bit s)
+  static int pred_weighting(const std::string& w) {
+    if (w == "period") return 0;
+    if (w == "pooled") return 1;
+    throw std::invalid_argument("weighting must be 'period' or 'pooled', not '" + w + "'");
+  }
+  // segment table, row weights c[t] and factor of split s (the device is quiescent: buffers are
+  // reallocated). c depends on row_ptr only: fp32(1 / (T' n_t)) over the T' non-empty periods, or
+  // fp32(1 / R) pooled.
+  void pred_prepare(int s, const py::object& factor, int weighting) {
+    FitSplit& S = fit_[s];
+    const SplitDev& D = splits_[s];
+    if (D.T > 65535) throw std::invalid_argument("prediction towers: more than 65535 periods");
+    std::vector<int> rp((size_t)D.T + 1, 0);
+    if (D.T > 0) HIP_LEGACY(hipMemcpy(rp.data(), D.row_ptr.p, rp.size() * sizeof(int), hipMemcpyDeviceToHost));
+    S.n.assign(D.T, 0);
+    int Tp = 0;
+    for (int t = 0; t < D.T; ++t) {
+      S.n[t] = rp[t + 1] - rp[t];
+      if (S.n[t] < 0 || rp[t + 1] > D.R) throw std::runtime_error("prediction towers: inconsistent row_ptr");
+      Tp += S.n[t] > 0;
+    }
+    std::vector<float> c(D.T, 0.f);
+    for (int t = 0; t < D.T; ++t) {
+      if (weighting == 1) c[t] = D.R > 0 ? (float)(1.0 / (double)D.R) : 0.f;
+      else c[t] = S.n[t] > 0 ? (float)(1.0 / ((double)Tp * (double)S.n[t])) : 0.f;
+    }
+    up(S.c, c.data(), c.size());
+    S.nseg = D.T > 0 ? lin_segments(D, S.seg, S.seg_ptr) : 0;
+    S.has_f = !factor.is_none();
+    if (S.has_f) {
+      auto f = py::array_t<float, py::array::c_style | py::array::forcecast>::ensure(factor);
+      if (!f || f.ndim() != 1 || f.shape(0) != D.T) throw std::invalid_argument("prediction towers: factor must be float32 [T]");
+      up(S.f, f.data(), (size_t)D.T);
+    }
+    S.ready = true;
+  }
+  void pred_alloc_models() {
+    if ((int)fitm_.size() != G_) { fitm_.clear(); fitm_.resize(G_); }
+    for (int g = 0; g < G_; ++g) {
+      FitModel& M = fitm_[g];
+      for (int s = 0; s < 3; ++s) {
+        if (!fit_[s].ready) continue;
+        M.part[s].alloc(std::max<size_t>((size_t)fit_[s].nseg * PRED_NSUM, 1));
+        M.sums[s].alloc(std::max<size_t>((size_t)PRED_NSUM * splits_[s].T, 1));
+      }
+      if (!M.loss.p) {
+        M.loss.alloc(3); M.hist.alloc((size_t)std::max(max_epochs_, 1) * PRED_HIST_W); M.best.alloc(1);
+        M.snap.alloc(md_.P); M.ep.alloc(2);
+      }
+    }
+  }
+  void pred_build_end() {
+    for (int s = 0; s < 3; ++s) {
+      if (!fit_[s].ready) continue;
+      std::vector<PredJob> pj(G_);
+      for (int g = 0; g < G_; ++g) {
+        pj[g].w = ws(g, s).w.p;
+        pj[g].dw = s == 0 ? ws(g, 0).dw.p : nullptr;
+        pj[g].part = fitm_[g].part[s].p;
+      }
+      upload(fit_[s].jobs, pj);
+    }
+    std::vector<PredEndJob> ej(G_);
+    for (int g = 0; g < G_; ++g) {
+      FitModel& M = fitm_[g];
+      PredEndJob E{};
+      for (int s = 0; s < 3; ++s) {
+        if (!fit_[s].ready) continue;
+        E.sp[s].part = M.part[s].p; E.sp[s].sums = M.sums[s].p; E.sp[s].c = fit_[s].c.p;
+        E.sp[s].seg_ptr = fit_[s].seg_ptr.p; E.sp[s].T = splits_[s].T;
+      }
+      E.loss = M.loss.p; E.hist = M.hist.p; E.ep = M.ep.p; E.best = M.best.p;
+      E.gnorm = models_[g].gnorm.p; E.params = models_[g].params.p; E.snap = M.snap.p;
+      E.prog = prog_ptr(g, 0); E.max_ep = max_epochs_;
+      ej[g] = E;
+    }
+    upload(j_pred_end_, ej);
+  }
+  PredArgs pred_args(int s) {
+    const FitSplit& S = fit_[s];
+    const SplitDev& D = splits_[s];
+    PredArgs A{};
+    A.jobs = as<PredJob>(S.jobs); A.Rc = D.Rc.p; A.f = S.has_f ? S.f.p : nullptr; A.c = S.c.p;
+    A.row_ptr = D.row_ptr.p; A.seg = reinterpret_cast<const int2*>(S.seg.p); A.nseg = S.nseg;
+    return A;
   }
 };
 
@@ -2939,6 +3197,14 @@ PYBIND11_MODULE(_dlap_hip, m) {
       .def("linear_portfolios", &Engine::linear_portfolios, py::arg("s"), py::arg("theta"),
            py::arg("center") = py::none(), py::arg("w_out") = 0)
       .def("linear_supported", &Engine::linear_supported)
+      .def("pred_loss", &Engine::pred_loss, py::arg("s"), py::arg("factor") = py::none(),
+           py::arg("weighting") = "period", py::arg("refresh") = true, py::arg("write_dw") = false)
+      .def("fit_begin", &Engine::fit_begin, py::arg("factors"), py::arg("weighting") = "period")
+      .def("fit_epochs", &Engine::fit_epochs, py::arg("n"), py::arg("lr"), py::call_guard<py::gil_scoped_release>())
+      .def("fit_history", &Engine::fit_history)
+      .def("fit_best", &Engine::fit_best)
+      .def("fit_load_best", &Engine::fit_load_best)
+      .def("apply_update", &Engine::apply_update)
       .def("weight_surface", &Engine::weight_surface, py::arg("s"), py::arg("scale"), py::arg("grid"), py::arg("base"),
            py::arg("items"), py::arg("refresh") = true)
       .def("weight_surface_supported", [](Engine& e, int s) { return e.wsurf_ok(s); }, py::arg("s") = 0)

@@ -41,8 +41,8 @@ built from a default spec) and the wide layer-0 path is covered. The kernel form
 (exact products, fp32 accumulation on the fp32-input MFMA) and ``v = float32(w - c)``; its sums are
 the fp64 sums of exactly the ``v`` it writes (``S1 = sum (v + c)``).
 
-Out of scope: the FFN return-prediction benchmark, a beta network, estimation on the GPU, value
-weighting, plots.
+The FFN return-prediction benchmark and the beta network live in ``analysis.prediction``. Out of
+scope here: estimation on the GPU, value weighting, plots.
 """
 from __future__ import annotations
 
@@ -429,16 +429,19 @@ def linear_benchmarks(batches: Dict[str, Dict], device: str = "cpu", center: str
     return out
 
 
-def format_benchmarks(res: Dict, gan: Optional[Dict] = None) -> List[str]:
-    """The printed table: rows LS, EN and (``gan``: ``train_sharpe``, ``valid_sharpe``,
-    ``test_sharpe``, ``ev``, ``xs_r2``) the GAN ensemble; columns Sharpe on train, valid and test,
-    then EV and XS-R2 on test."""
+def format_benchmarks(res: Dict, gan: Optional[Dict] = None, ffn: Optional[Dict] = None) -> List[str]:
+    """The printed table: rows LS, EN, (``ffn``: a row of ``prediction.ffn_benchmark``) FFN and
+    (``gan``: ``train_sharpe``, ``valid_sharpe``, ``test_sharpe``, ``ev``, ``xs_r2``) the GAN ensemble;
+    columns Sharpe on train, valid and test, then EV and XS-R2 on test."""
     lines = [f"  {'':14s} {'SR train':>9s} {'SR valid':>9s} {'SR test':>9s} {'EV test':>9s} {'XS-R2 test':>11s}"]
     for key in ("LS", "EN"):
         if key in res:
             o = res[key]
             lines.append(f"  {key:14s} {o['sharpe']['train']:9.4f} {o['sharpe']['valid']:9.4f} {o['sharpe']['test']:9.4f} "
                          f"{o['ev']['test']:9.4f} {o['xs_r2']['test']:11.4f}")
+    if ffn is not None:
+        from .prediction import format_ffn_row
+        lines.append(format_ffn_row(ffn))
     if gan is not None:
         lines.append(f"  {'GAN ensemble':14s} {gan['train_sharpe']:9.4f} {gan['valid_sharpe']:9.4f} {gan['test_sharpe']:9.4f} "
                      f"{gan['ev']:9.4f} {gan['xs_r2']:11.4f}")
@@ -463,9 +466,9 @@ def _jsonable(v):
     return v
 
 
-def to_json(res: Dict, gan: Optional[Dict] = None) -> Dict:
+def to_json(res: Dict, gan: Optional[Dict] = None, ffn: Optional[Dict] = None) -> Dict:
     """Plain lists (non-finite values as null): every row without its dense weights, the
-    candidates' penalties and Sharpe ratios, and ``gan`` when given."""
+    candidates' penalties and Sharpe ratios, and ``gan`` / ``ffn`` (key ``FFN``) when given."""
     out = {"device": res["device"], "center": res["center"]}
     for key in ("LS", "EN"):
         if key in res:
@@ -473,6 +476,8 @@ def to_json(res: Dict, gan: Optional[Dict] = None) -> Dict:
     c = res["candidates"]
     out["candidates"] = _jsonable({k: (v if k not in SPLITS else {"sharpe": v["sharpe"], "ev": v["ev"]})
                                    for k, v in c.items()})
+    if ffn is not None:
+        out["FFN"] = _jsonable({k: v for k, v in ffn.items() if k != "weights"})
     if gan is not None:
         out["GAN"] = _jsonable(gan)
     return out

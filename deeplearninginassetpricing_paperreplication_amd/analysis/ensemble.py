@@ -95,7 +95,9 @@ def evaluate_ensemble(checkpoint_dirs: Sequence[str], data_dir: str, device: str
                       structure_pairs=None, structure_out: str = None, double_sorts=None,
                       double_quantiles=(5, 5), double_mode: str = "conditional", double_out: str = None,
                       benchmarks: bool = False, benchmark_grid=(16, 4), benchmark_center: str = "mean",
-                      benchmarks_out: str = None) -> Dict:
+                      benchmarks_out: str = None, benchmark_ffn: bool = False, beta_network: bool = False,
+                      prediction_epochs: int = 64, prediction_lr: float = None, prediction_seeds=(0,),
+                      prediction_out: str = None) -> Dict:
     """Reference output and return value; ``paper=True`` (CLI ``--paper_metrics``) adds the
     paper's EV / XS-R² / turnover / max 1-month loss of the ensemble's SDF factor per split;
     ``importance=True`` (CLI ``--variable_importance``) adds the sensitivity ranking of the
@@ -120,7 +122,15 @@ def evaluate_ensemble(checkpoint_dirs: Sequence[str], data_dir: str, device: str
     ``benchmarks=True`` (CLI ``--benchmarks``) adds the linear (LS) and elastic-net (EN) benchmark
     SDFs (``analysis.benchmarks``: EN over the ``benchmark_grid`` = (n1, n2) penalties, selected on
     the validation split; ``benchmark_center``: ``mean`` or ``none``) next to the ensemble in one
-    table, under the key ``benchmarks``, and writes them to ``benchmarks_out`` (JSON) when given."""
+    table, under the key ``benchmarks``, and writes them to ``benchmarks_out`` (JSON) when given;
+    ``benchmark_ffn=True`` (CLI ``--benchmark_ffn``, with ``benchmarks``) adds the FFN
+    return-prediction benchmark (``analysis.prediction.ffn_benchmark``) as a row between EN and the
+    ensemble (key ``benchmarks["ffn"]``, ``FFN`` in the JSON);
+    ``beta_network=True`` (CLI ``--beta_network``) fits the beta network to the ensemble's SDF factor
+    (``analysis.prediction.beta_network``) and prints EV / XS-R² with its loadings per split next to
+    the proxy figures, under the key ``beta_network``. Both towers take the architecture of the
+    first checkpoint's config and ``prediction_epochs`` / ``prediction_lr`` / ``prediction_seeds``;
+    ``prediction_out`` (JSON) holds whichever of the two ran."""
     say = print if verbose else (lambda *a, **k: None)
     bar = "=" * 70
     say(bar); say(f"ENSEMBLE EVALUATION ({len(checkpoint_dirs)} models, averaged weights)"); say(bar); say()
@@ -248,6 +258,9 @@ def evaluate_ensemble(checkpoint_dirs: Sequence[str], data_dir: str, device: str
             with open(double_out, "w") as fh:
                 json.dump(sp.double_to_json(res_ds, priced), fh, indent=1)
             say(f"  Saved: {double_out}"); say()
+    pred_json = {}
+    if benchmark_ffn and not benchmarks:
+        raise ValueError("benchmark_ffn needs benchmarks (CLI: --benchmark_ffn with --benchmarks)")
     if benchmarks:
         from . import benchmarks as bm
         from .portfolio import cross_sectional_r2, explained_variation
@@ -261,14 +274,46 @@ def evaluate_ensemble(checkpoint_dirs: Sequence[str], data_dir: str, device: str
                "ev": explained_variation(wavg, tb["returns"], tb["mask"]),
                "xs_r2": cross_sectional_r2(wavg, tb["returns"], tb["mask"])}
         out["benchmarks"] = {"linear": res_bm, "gan": gan}
+        ffn_kw = {}
+        if benchmark_ffn:
+            from . import prediction as pred
+            ffn = pred.ffn_benchmark(batches, models[0].config, device=device, epochs=prediction_epochs,
+                                     lr=prediction_lr, seeds=tuple(prediction_seeds))
+            out["benchmarks"]["ffn"] = pred_json["FFN"] = ffn
+            ffn_kw = {"ffn": ffn}
         say(bar); say("BENCHMARK SDFS (linear LS / elastic net EN vs the ensemble)"); say(bar); say()
-        for line in bm.format_benchmarks(res_bm, gan):
+        for line in bm.format_benchmarks(res_bm, gan, **ffn_kw):
             say(line)
         say()
         if benchmarks_out:
             with open(benchmarks_out, "w") as fh:
-                json.dump(bm.to_json(res_bm, gan), fh, indent=1)
+                json.dump(bm.to_json(res_bm, gan, **ffn_kw), fh, indent=1)
             say(f"  Saved: {benchmarks_out}"); say()
+    if beta_network:
+        from . import prediction as pred
+        from .portfolio import cross_sectional_r2, explained_variation
+        wavg, proxy = {}, {}
+        for s in SPLITS:
+            b = np_batches[s]
+            if str(device).startswith("cuda"):
+                wavg[s] = average_weights(list(wdev[s].cpu().numpy()), b["mask"])
+            else:
+                wavg[s] = average_weights([w[s] for w in weights], b["mask"])
+            proxy[s] = {"ev": explained_variation(wavg[s], b["returns"], b["mask"]),
+                        "xs_r2": cross_sectional_r2(wavg[s], b["returns"], b["mask"])}
+        res_bn = pred.beta_network(wavg, batches, models[0].config, device=device, epochs=prediction_epochs,
+                                   lr=prediction_lr, seeds=tuple(prediction_seeds))
+        res_bn["proxy"] = proxy
+        out["beta_network"] = pred_json["beta_network"] = res_bn
+        say(bar); say("BETA NETWORK (EV / XS-R2 with fitted loadings vs the SDF-weight proxy)"); say(bar); say()
+        for line in pred.format_beta(res_bn, proxy):
+            say(line)
+        say()
+    if prediction_out and pred_json:
+        from . import prediction as pred
+        with open(prediction_out, "w") as fh:
+            json.dump({k: pred.to_json(v) for k, v in pred_json.items()}, fh, indent=1)
+        say(f"  Saved: {prediction_out}"); say()
     if weight_structure:
         from . import weight_structure as wst
         if structure_split not in SPLITS:
@@ -324,6 +369,14 @@ def _parser():
     p.add_argument("--benchmark_grid", type=str, default="16x4", help="EN penalties: N1xN2 values of l1 x l2 (N2 <= 4)")
     p.add_argument("--benchmark_center", type=str, default="mean", choices=("mean", "none"))
     p.add_argument("--benchmarks_out", type=str, default=None, help="write the benchmark results to FILE.json")
+    p.add_argument("--benchmark_ffn", action="store_true",
+                   help="with --benchmarks: also fit the FFN return-prediction benchmark (a row between EN and the ensemble)")
+    p.add_argument("--beta_network", action="store_true",
+                   help="also fit the beta network to the ensemble's SDF factor and print EV / XS-R2 with its loadings")
+    p.add_argument("--prediction_epochs", type=int, default=64, help="fit epochs of the FFN benchmark / beta network")
+    p.add_argument("--prediction_lr", type=float, default=None, help="their learning rate (default: 1e-3)")
+    p.add_argument("--prediction_seeds", type=int, nargs="+", default=[0], help="their seeds (predictions are averaged)")
+    p.add_argument("--prediction_out", type=str, default=None, help="write the FFN / beta-network results to FILE.json")
     return p
 
 
@@ -343,6 +396,12 @@ def _extra_kwargs(a) -> Dict:
         from .benchmarks import parse_grid
         kw.update(benchmarks=True, benchmark_grid=parse_grid(a.benchmark_grid), benchmark_center=a.benchmark_center,
                   benchmarks_out=a.benchmarks_out)
+    if a.benchmark_ffn or a.beta_network:
+        if a.benchmark_ffn and not a.benchmarks:
+            raise SystemExit("--benchmark_ffn needs --benchmarks")
+        kw.update(benchmark_ffn=a.benchmark_ffn, beta_network=a.beta_network, prediction_epochs=a.prediction_epochs,
+                  prediction_lr=a.prediction_lr, prediction_seeds=tuple(a.prediction_seeds),
+                  prediction_out=a.prediction_out)
     return kw
 
 

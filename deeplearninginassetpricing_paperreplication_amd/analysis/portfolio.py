@@ -114,7 +114,9 @@ def ensemble_sharpes_device(wstack: Dict, batches: Dict[str, Dict]) -> Dict:
 # turnover of Table A.VII, max 1-month loss of Table A.VI). The paper's loadings come from a
 # separate beta network; here the loading direction of period t is the SDF weight vector itself
 # (the cross-sectional projection the reference's residual loss uses, `model.py:435-483`),
-# which makes the metrics computable from any checkpoint's weights.
+# which makes the metrics computable from any checkpoint's weights. The paper's own figures, with
+# loadings from a fitted beta network, come from `analysis.prediction.beta_network`, which passes
+# its loadings to the same two functions.
 # ------------------------------------------------------------------------------------------
 def _projection_residuals(weights: np.ndarray, returns: np.ndarray, mask: np.ndarray) -> np.ndarray:
     m = mask.astype(np.float64)

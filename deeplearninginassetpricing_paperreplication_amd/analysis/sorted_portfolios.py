@@ -46,7 +46,8 @@ Double sorts (``double_sort_numpy`` is the definition, ``Engine.double_sorted_po
   ``A == B`` is legal and gets no special case.
 
 Out of scope: value-weighted buckets (the panel carries no market cap; ``sort_buckets_numpy`` and
-the engine methods accept further value columns), triple sorts, a beta network, plots.
+the engine methods accept further value columns), triple sorts, plots (the beta network:
+``analysis.prediction``).
 """
 from __future__ import annotations
 
