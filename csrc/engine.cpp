@@ -44,6 +44,7 @@
 #include "qsort.h"
 #include "qsort2.h"
 #include "linport.h"
+#include "xgram.h"
 #include "pred.h"
 #include "rnn.h"
 #include "update.h"
@@ -1133,6 +1134,52 @@ class Engine {
     py::dict d;
     d["s1"] = r1; d["sa"] = ra; d["s2"] = r2; d["sr"] = rr; d["n"] = nn; d["sum_r"] = sr; d["sum_rr"] = srr;
     d["rows"] = D.R; d["gpu_ms"] = ms;
+    return d;
+  }
+  // ---- characteristic Gram (k_xgram.hip, definitions in xgram.h and analysis/ipca.py) ----
+  // characteristic_gram: gram fp64 [T][F][F] (sum_i x x' over the valid rows of each period, x as
+  // the engine stores it; the lower triangle a bitwise mirror of the upper), n int32 [T], sum_r and
+  // sum_rr fp64 [T], rows (= R) and gpu_ms. Reads the panel only; repeated calls are bitwise
+  // identical. An empty split returns zeros and launches nothing.
+  int xgram_run() const { return ::xgram_run(); }
+  py::dict characteristic_gram(int s) {
+    if (s < 0 || s > 2) throw std::invalid_argument("split must be 0, 1 or 2");
+    const SplitDev& D = splits_[s];
+    if (!D.set) throw std::runtime_error("split not set");
+    if (D.T > 65535) throw std::invalid_argument("characteristic_gram: more than 65535 periods");
+    const int F = md_.F;
+    py::array_t<double> g({(py::ssize_t)D.T, (py::ssize_t)F, (py::ssize_t)F}), sr(D.T), srr(D.T);
+    py::array_t<int> nn(D.T);
+    for (auto* a : {&g, &sr, &srr}) std::fill_n(a->mutable_data(), a->size(), 0.0);
+    std::fill_n(nn.mutable_data(), nn.size(), 0);
+    float ms = 0.f;
+    if (D.R > 0 && D.T > 0) {
+      DevBuf<int> dtiles, dn;
+      DevBuf<double> dg, dr;
+      std::vector<int> tiles;
+      xgram_tiles(F, tiles);
+      up(dtiles, tiles.data(), tiles.size());
+      XgramArgs A{};
+      A.X = D.X.p; A.KP = md_.KP; A.fp32 = md_.md.fp32 ? 1 : 0; A.F = F;
+      A.Rc = D.Rc.p; A.row_ptr = D.row_ptr.p; A.T = D.T;
+      A.tiles = reinterpret_cast<const int2*>(dtiles.p); A.ntiles = (int)(tiles.size() / 2);
+      dg.alloc((size_t)g.size(), false); dr.alloc((size_t)2 * D.T, false); dn.alloc(D.T, false);
+      A.gram = dg.p; A.sum_r = dr.p; A.n = dn.p;
+      hipEvent_t ev[2];
+      for (auto& e : ev) HIP_OK(hipEventCreate(&e));
+      HIP_OK(hipEventRecord(ev[0], st_));
+      launch_xgram(A, st_);
+      HIP_OK(hipEventRecord(ev[1], st_));
+      sync();
+      HIP_OK(hipEventElapsedTime(&ms, ev[0], ev[1]));
+      for (auto& e : ev) HIP_OK(hipEventDestroy(e));
+      HIP_LEGACY(hipMemcpy(g.mutable_data(), dg.p, (size_t)g.size() * sizeof(double), hipMemcpyDeviceToHost));
+      HIP_LEGACY(hipMemcpy(sr.mutable_data(), dr.p, D.T * sizeof(double), hipMemcpyDeviceToHost));
+      HIP_LEGACY(hipMemcpy(srr.mutable_data(), dr.p + D.T, D.T * sizeof(double), hipMemcpyDeviceToHost));
+      HIP_LEGACY(hipMemcpy(nn.mutable_data(), dn.p, nn.size() * sizeof(int), hipMemcpyDeviceToHost));
+    }
+    py::dict d;
+    d["gram"] = g; d["n"] = nn; d["sum_r"] = sr; d["sum_rr"] = srr; d["rows"] = D.R; d["gpu_ms"] = ms;
     return d;
   }
   // ---- prediction towers (k_pred.hip, definitions in pred.h and analysis/prediction.py) ----
@@ -3197,6 +3244,8 @@ PYBIND11_MODULE(_dlap_hip, m) {
       .def("linear_portfolios", &Engine::linear_portfolios, py::arg("s"), py::arg("theta"),
            py::arg("center") = py::none(), py::arg("w_out") = 0)
       .def("linear_supported", &Engine::linear_supported)
+      .def("characteristic_gram", &Engine::characteristic_gram, py::arg("s"))
+      .def("xgram_run", &Engine::xgram_run)
       .def("pred_loss", &Engine::pred_loss, py::arg("s"), py::arg("factor") = py::none(),
            py::arg("weighting") = "period", py::arg("refresh") = true, py::arg("write_dw") = false)
       .def("fit_begin", &Engine::fit_begin, py::arg("factors"), py::arg("weighting") = "period")

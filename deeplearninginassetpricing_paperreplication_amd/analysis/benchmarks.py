@@ -41,7 +41,8 @@ built from a default spec) and the wide layer-0 path is covered. The kernel form
 (exact products, fp32 accumulation on the fp32-input MFMA) and ``v = float32(w - c)``; its sums are
 the fp64 sums of exactly the ``v`` it writes (``S1 = sum (v + c)``).
 
-The FFN return-prediction benchmark and the beta network live in ``analysis.prediction``. Out of
+The FFN return-prediction benchmark and the beta network live in ``analysis.prediction``, IPCA and
+Fama-MacBeth (on the per-period characteristic Gram, ``gram`` of the panel objects) in ``analysis.ipca``. Out of
 scope here: estimation on the GPU, value weighting, plots.
 """
 from __future__ import annotations
@@ -258,6 +259,11 @@ class _CpuPanel:
         b = self.b[s]
         return managed_portfolios_numpy(b["x"], b["r"], b["m"])
 
+    def gram(self, s: int) -> Dict:
+        from .ipca import characteristic_gram_numpy
+        b = self.b[s]
+        return characteristic_gram_numpy(b["x"], b["r"], b["m"])
+
     def sums(self, s: int, th: np.ndarray, c, weights: bool) -> Dict:
         b = self.b[s]
         return linear_sums_numpy(b["x"], b["r"], b["m"], th, c, weights)
@@ -289,6 +295,11 @@ class _GpuPanel:
         r = self.eng.eng.managed_portfolios(s)
         return {"sum_x": np.asarray(r["sum_x"]), "sum_xr": np.asarray(r["sum_xr"]), "n": np.asarray(r["n"]),
                 "rows": int(r["rows"]), "gpu_ms": float(r["gpu_ms"])}
+
+    def gram(self, s: int) -> Dict:
+        r = self.eng.eng.characteristic_gram(s)
+        return {"gram": np.asarray(r["gram"]), "n": np.asarray(r["n"]), "sum_r": np.asarray(r["sum_r"]),
+                "sum_rr": np.asarray(r["sum_rr"]), "rows": int(r["rows"]), "gpu_ms": float(r["gpu_ms"])}
 
     def sums(self, s: int, th: np.ndarray, c, weights: bool) -> Dict:
         T, N = self.shapes[s]
@@ -429,16 +440,21 @@ def linear_benchmarks(batches: Dict[str, Dict], device: str = "cpu", center: str
     return out
 
 
-def format_benchmarks(res: Dict, gan: Optional[Dict] = None, ffn: Optional[Dict] = None) -> List[str]:
-    """The printed table: rows LS, EN, (``ffn``: a row of ``prediction.ffn_benchmark``) FFN and
-    (``gan``: ``train_sharpe``, ``valid_sharpe``, ``test_sharpe``, ``ev``, ``xs_r2``) the GAN ensemble;
-    columns Sharpe on train, valid and test, then EV and XS-R2 on test."""
+def format_benchmarks(res: Dict, gan: Optional[Dict] = None, ffn: Optional[Dict] = None,
+                      ipca: Optional[Dict] = None) -> List[str]:
+    """The printed table: rows LS, EN, (``ipca``: a row of ``ipca.ipca_benchmark``) IPCA,
+    (``ffn``: a row of ``prediction.ffn_benchmark``) FFN and (``gan``: ``train_sharpe``,
+    ``valid_sharpe``, ``test_sharpe``, ``ev``, ``xs_r2``) the GAN ensemble; columns Sharpe on train,
+    valid and test, then EV and XS-R2 on test."""
     lines = [f"  {'':14s} {'SR train':>9s} {'SR valid':>9s} {'SR test':>9s} {'EV test':>9s} {'XS-R2 test':>11s}"]
     for key in ("LS", "EN"):
         if key in res:
             o = res[key]
             lines.append(f"  {key:14s} {o['sharpe']['train']:9.4f} {o['sharpe']['valid']:9.4f} {o['sharpe']['test']:9.4f} "
                          f"{o['ev']['test']:9.4f} {o['xs_r2']['test']:11.4f}")
+    if ipca is not None:
+        from .ipca import format_ipca_row
+        lines.append(format_ipca_row(ipca))
     if ffn is not None:
         from .prediction import format_ffn_row
         lines.append(format_ffn_row(ffn))
@@ -466,9 +482,10 @@ def _jsonable(v):
     return v
 
 
-def to_json(res: Dict, gan: Optional[Dict] = None, ffn: Optional[Dict] = None) -> Dict:
+def to_json(res: Dict, gan: Optional[Dict] = None, ffn: Optional[Dict] = None, ipca: Optional[Dict] = None) -> Dict:
     """Plain lists (non-finite values as null): every row without its dense weights, the
-    candidates' penalties and Sharpe ratios, and ``gan`` / ``ffn`` (key ``FFN``) when given."""
+    candidates' penalties and Sharpe ratios, and ``gan`` / ``ffn`` (key ``FFN``) / ``ipca`` (key
+    ``IPCA``) when given."""
     out = {"device": res["device"], "center": res["center"]}
     for key in ("LS", "EN"):
         if key in res:
@@ -476,6 +493,8 @@ def to_json(res: Dict, gan: Optional[Dict] = None, ffn: Optional[Dict] = None) -
     c = res["candidates"]
     out["candidates"] = _jsonable({k: (v if k not in SPLITS else {"sharpe": v["sharpe"], "ev": v["ev"]})
                                    for k, v in c.items()})
+    if ipca is not None:
+        out["IPCA"] = _jsonable({k: v for k, v in ipca.items() if k != "weights"})
     if ffn is not None:
         out["FFN"] = _jsonable({k: v for k, v in ffn.items() if k != "weights"})
     if gan is not None:

@@ -97,7 +97,8 @@ def evaluate_ensemble(checkpoint_dirs: Sequence[str], data_dir: str, device: str
                       benchmarks: bool = False, benchmark_grid=(16, 4), benchmark_center: str = "mean",
                       benchmarks_out: str = None, benchmark_ffn: bool = False, beta_network: bool = False,
                       prediction_epochs: int = 64, prediction_lr: float = None, prediction_seeds=(0,),
-                      prediction_out: str = None) -> Dict:
+                      prediction_out: str = None, benchmark_ipca: bool = False, ipca_factors=(1, 2, 3, 4, 5, 6),
+                      ipca_intercept: bool = True, fama_macbeth: bool = False, fm_out: str = None) -> Dict:
     """Reference output and return value; ``paper=True`` (CLI ``--paper_metrics``) adds the
     paper's EV / XS-R² / turnover / max 1-month loss of the ensemble's SDF factor per split;
     ``importance=True`` (CLI ``--variable_importance``) adds the sensitivity ranking of the
@@ -130,7 +131,15 @@ def evaluate_ensemble(checkpoint_dirs: Sequence[str], data_dir: str, device: str
     (``analysis.prediction.beta_network``) and prints EV / XS-R² with its loadings per split next to
     the proxy figures, under the key ``beta_network``. Both towers take the architecture of the
     first checkpoint's config and ``prediction_epochs`` / ``prediction_lr`` / ``prediction_seeds``;
-    ``prediction_out`` (JSON) holds whichever of the two ran."""
+    ``prediction_out`` (JSON) holds whichever of the two ran;
+    ``benchmark_ipca=True`` (CLI ``--benchmark_ipca``, with ``benchmarks``) adds the IPCA benchmark
+    (``analysis.ipca.ipca_benchmark``: ``ipca_factors`` candidates of ``K``, selected on the validation
+    split; ``ipca_intercept``) as a row ``IPCA (K=k)`` between EN and FFN (key ``benchmarks["ipca"]``,
+    ``IPCA`` in the JSON);
+    ``fama_macbeth=True`` (CLI ``--fama_macbeth``) prints the Fama-MacBeth slope table of ``sort_split``
+    (``analysis.ipca.fama_macbeth``), under the key ``fama_macbeth``, and writes it to ``fm_out`` (JSON)
+    when given. Both use the per-period characteristic Gram: ``Engine.characteristic_gram`` with
+    ``device="cuda"``, numpy otherwise."""
     say = print if verbose else (lambda *a, **k: None)
     bar = "=" * 70
     say(bar); say(f"ENSEMBLE EVALUATION ({len(checkpoint_dirs)} models, averaged weights)"); say(bar); say()
@@ -261,6 +270,8 @@ def evaluate_ensemble(checkpoint_dirs: Sequence[str], data_dir: str, device: str
     pred_json = {}
     if benchmark_ffn and not benchmarks:
         raise ValueError("benchmark_ffn needs benchmarks (CLI: --benchmark_ffn with --benchmarks)")
+    if benchmark_ipca and not benchmarks:
+        raise ValueError("benchmark_ipca needs benchmarks (CLI: --benchmark_ipca with --benchmarks)")
     if benchmarks:
         from . import benchmarks as bm
         from .portfolio import cross_sectional_r2, explained_variation
@@ -281,6 +292,11 @@ def evaluate_ensemble(checkpoint_dirs: Sequence[str], data_dir: str, device: str
                                      lr=prediction_lr, seeds=tuple(prediction_seeds))
             out["benchmarks"]["ffn"] = pred_json["FFN"] = ffn
             ffn_kw = {"ffn": ffn}
+        if benchmark_ipca:
+            from . import ipca as ip
+            row = ip.ipca_benchmark(batches, factors=tuple(ipca_factors), intercept=ipca_intercept, device=device)
+            out["benchmarks"]["ipca"] = row
+            ffn_kw["ipca"] = row
         say(bar); say("BENCHMARK SDFS (linear LS / elastic net EN vs the ensemble)"); say(bar); say()
         for line in bm.format_benchmarks(res_bm, gan, **ffn_kw):
             say(line)
@@ -289,6 +305,21 @@ def evaluate_ensemble(checkpoint_dirs: Sequence[str], data_dir: str, device: str
             with open(benchmarks_out, "w") as fh:
                 json.dump(bm.to_json(res_bm, gan, **ffn_kw), fh, indent=1)
             say(f"  Saved: {benchmarks_out}"); say()
+    if fama_macbeth:
+        from . import ipca as ip
+        if sort_split not in SPLITS:
+            raise ValueError(f"sort_split must be one of {SPLITS}")
+        names = getattr(datasets[SPLITS.index(sort_split)], "variable_names", None)
+        res_fm = ip.fama_macbeth(batches[sort_split], intercept=ipca_intercept, device=device)
+        out["fama_macbeth"] = res_fm
+        say(bar); say(f"FAMA-MACBETH REGRESSIONS ({sort_split} split)"); say(bar); say()
+        for line in ip.format_fama_macbeth(res_fm, names):
+            say(line)
+        say()
+        if fm_out:
+            with open(fm_out, "w") as fh:
+                json.dump(ip.fama_macbeth_json(res_fm, names), fh, indent=1)
+            say(f"  Saved: {fm_out}"); say()
     if beta_network:
         from . import prediction as pred
         from .portfolio import cross_sectional_r2, explained_variation
@@ -377,6 +408,15 @@ def _parser():
     p.add_argument("--prediction_lr", type=float, default=None, help="their learning rate (default: 1e-3)")
     p.add_argument("--prediction_seeds", type=int, nargs="+", default=[0], help="their seeds (predictions are averaged)")
     p.add_argument("--prediction_out", type=str, default=None, help="write the FFN / beta-network results to FILE.json")
+    p.add_argument("--benchmark_ipca", action="store_true",
+                   help="with --benchmarks: also estimate the IPCA benchmark (a row between EN and FFN)")
+    p.add_argument("--ipca_factors", type=int, nargs="+", default=[1, 2, 3, 4, 5, 6],
+                   help="candidate numbers of IPCA factors (selected on the validation split)")
+    p.add_argument("--ipca_no_intercept", action="store_true",
+                   help="IPCA / Fama-MacBeth without the constant column")
+    p.add_argument("--fama_macbeth", action="store_true",
+                   help="also print the Fama-MacBeth slope table of --sort_split")
+    p.add_argument("--fm_out", type=str, default=None, help="write the Fama-MacBeth table to FILE.json")
     return p
 
 
@@ -402,6 +442,12 @@ def _extra_kwargs(a) -> Dict:
         kw.update(benchmark_ffn=a.benchmark_ffn, beta_network=a.beta_network, prediction_epochs=a.prediction_epochs,
                   prediction_lr=a.prediction_lr, prediction_seeds=tuple(a.prediction_seeds),
                   prediction_out=a.prediction_out)
+    if a.benchmark_ipca:
+        if not a.benchmarks:
+            raise SystemExit("--benchmark_ipca needs --benchmarks")
+        kw.update(benchmark_ipca=True, ipca_factors=tuple(a.ipca_factors), ipca_intercept=not a.ipca_no_intercept)
+    if a.fama_macbeth:
+        kw.update(fama_macbeth=True, fm_out=a.fm_out, sort_split=a.sort_split, ipca_intercept=not a.ipca_no_intercept)
     return kw
 
 
