@@ -40,6 +40,7 @@
 #include "loss.h"
 #include "macro_sens.h"
 #include "mlp.h"
+#include "mlstm.h"
 #include "panel.h"
 #include "qsort.h"
 #include "qsort2.h"
@@ -167,6 +168,8 @@ struct ModelSplitWS {   // per (model, split)
   DevBuf<float> h0, c0;       // [nrnn][H] initial LSTM state of the split (zero unless set_hidden)
   DevBuf<float> dh0, dc0;     // train split: dL/d(initial state) from the last LSTM backward
   DevBuf<float> dhx;          // train split, module API: external dL/dh [T*N][K] (lazy)
+  DevBuf<float> mxg, mhm;     // moment LSTM: input projections [T][4Hm], outputs [T][Hm]
+  DevBuf<float> msg, msc, mdg, mdhm;   // ... train split: saved gates / cells, gate and output gradients
   DevBuf<double> gram;        // Gram mode: [2][T][T] Gc, Gu of the frozen moments (k_gram.hip)
   DevBuf<double> gpart;       // Gram mode: [T][2] per-period quadratic-form terms
   DevBuf<float> xs;           // sharded engine: [4][T] per-period partial sums + [2] loss sums
@@ -195,8 +198,9 @@ class Engine {
  public:
   Engine(int F, int M, int nrnn, int H, bool raw_macro_sdf, std::vector<int> hidden,
          std::vector<int> mom_hidden, int K, float dropout, bool normalize_w, bool weighted,
-         float residual, int G, int max_epochs, bool fp32)
+         float residual, int G, int max_epochs, bool fp32, int mom_nrnn = 0, int mom_H = 0)
       : G_(G), max_epochs_(max_epochs), k_(read_knobs(G, fp32)) {
+    check_mom_lstm(F, M, nrnn > 0 ? H : (raw_macro_sdf ? M : 0), mom_nrnn, mom_H);
     g_live_engines.fetch_add(1);
     HIP_OK(hipStreamCreateWithFlags(&st_, hipStreamNonBlocking));
     {
@@ -219,7 +223,7 @@ class Engine {
     own_st_ = st_;
     for (hipEvent_t& e : ev_) HIP_OK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     build_desc(F, M, nrnn, H, raw_macro_sdf, hidden, mom_hidden, K, dropout, normalize_w, weighted,
-               residual, fp32);
+               residual, fp32, mom_nrnn, mom_H);
     prog_.alloc((size_t)G * 3 * 16);      // per (model, split): [0] published periods, [1] spin timeouts
     esync_.alloc(64);                      // split epoch graphs: [0] evaluation recurrences done, [32] consumed
     d_desc_.alloc(sizeof(ModelDesc));
@@ -243,6 +247,22 @@ class Engine {
     build_pack_inverse();
     upload_pack_jobs();
   }
+  // The moment network's own macro LSTM (k_mlstm.hip): one layer of width 1..DLAP_MAX_MH over
+  // M >= 1 macro series; mom_nrnn = 0 (and mom_H = 0): none. Checked before anything is allocated.
+  void check_mom_lstm(int F, int M, int Dm, int mom_nrnn, int mom_H) const {
+    if (mom_nrnn == 0 && mom_H == 0) return;
+    if (mom_nrnn != 1)
+      throw std::invalid_argument("moment LSTM: the native engine supports exactly 1 layer (mom_nrnn == 1), got " +
+                                  std::to_string(mom_nrnn));
+    if (mom_H < 1 || mom_H > DLAP_MAX_MH)
+      throw std::invalid_argument("moment LSTM: width mom_H must be in [1, " + std::to_string(DLAP_MAX_MH) +
+                                  "], got " + std::to_string(mom_H));
+    if (M < 1) throw std::invalid_argument("moment LSTM: needs M >= 1 macro series");
+    if (k_.wide || (F + (Dm + 7) / 8 * 8 + 31) / 32 > 4)       // (build_desc's choice of the path)
+      throw std::invalid_argument("moment LSTM: the wide layer-0 path (DLAP_WIDE=1, or more than 128 layer-0 "
+                                  "input columns) is not supported with it");
+  }
+  bool mlstm() const { return md_.mH > 0; }
   // Scatter lists of the fused re-pack: pack_index_host names the parameter behind every packed
   // element (from the same gathers k_pack uses), inverted here into
   // fixed-width lists per parameter (PACK_FAN slots). Without them (DLAP_FUSED_PACK=0, indices
@@ -296,6 +316,7 @@ class Engine {
     d["Dm"] = md_.Dm; d["blob_frags"] = md_.md.blob_frags; d["aux_floats"] = md_.md.aux_floats;
     d["ntile_s"] = md_.ntile_s; d["tps_s"] = md_.tps_s; d["tbwd"] = md_.tbwd; d["ntile_m"] = md_.ntile_m; d["G"] = G_;
     d["wide"] = md_.md.wide; d["KX"] = md_.md.KX; d["nsplit"] = nsplit_; d["fp32"] = md_.md.fp32;
+    d["mom_nrnn"] = md_.mnrnn; d["mom_H"] = md_.mH;
     return d;
   }
 
@@ -1433,6 +1454,8 @@ class Engine {
   // instead of dE / sdf -- a caller's loss of the moments.
   void xs_backward(int phase, uintptr_t dw, uintptr_t dE, uintptr_t sdf, uintptr_t dh = 0) {
     check_phase(phase);
+    if (mlstm())
+      throw std::invalid_argument("moment LSTM: the external-gradient backward (xs_backward) is not supported with it");
     ensure_jobs();
     if (dh) {
       if (phase != 2) throw std::invalid_argument("an external dL/dh needs phase 2 (the moment tower)");
@@ -1671,6 +1694,8 @@ class Engine {
   // quadratic forms, Adam). Pipelined / split epoch graphs and the fused tail are off; phases 1
   // and 3 use the Gram-form losses (no per-epoch loss all-reduce at all).
   void set_xs(py::object hook) {
+    if (mlstm() && !hook.is_none())
+      throw std::invalid_argument("moment LSTM: cross-sectional sharding (set_xs) is not supported with it");
     xs_on_ = !hook.is_none();
     xs_hook_ = hook;
     if (xs_on_) pipeline_ = false;
@@ -1715,7 +1740,7 @@ class Engine {
   bool ext_stream_ = false;
   DevBuf<char> j_pack_;                      // per-model re-pack jobs
   DevBuf<int> inv_code_;                     // parameter -> packed elements (k_adam's fused re-pack)
-  struct FwdTables { DevBuf<char> r, m, l, w; bool built = false; };
+  struct FwdTables { DevBuf<char> r, m, l, w, ml; bool built = false; };
   std::map<int, FwdTables> fwd_tables_;      // module-API forward job tables (per split / mode)
   hipStream_t st2_ = nullptr;                // evaluation branch of the pipelined epoch graph
   // fork / join of the two streams, after the loss pass, after the tower forward, join_from /
@@ -1863,7 +1888,8 @@ class Engine {
       // Phase 2: k_finalize -> k_wgrad -> k_adam and the train metrics as ONE launch (k_lstm_tail,
       // phase 2: the per-period sums relayed to the W_macro helpers, the moment network's clip + Adam
       // in the last blocks); the frozen SDF's LSTM recurrence once per run_epochs call
-      p.mom_tail = phase == 2 && k_.mom_tail && !xs_on_ && packs && have0 && mom_tail_supported(md_, splits_[0].T);
+      p.mom_tail = phase == 2 && k_.mom_tail && !xs_on_ && packs && have0 && mom_tail_supported(md_, splits_[0].T) &&
+                   !mlstm();      // (moment LSTM: k_finalize -> launch_mlstm_bwd -> k_adam)
       p.p2_lstm_cached = phase == 2 && k_.p2_lstm_cache && md_.nrnn > 0 && (md_.nrnn == 1 || md_.dropout == 0.f) &&
                          !xs_on_;
       plan_[phase] = p;
@@ -1958,6 +1984,8 @@ class Engine {
       j_loss_eval_, j_fin_, j_upd_, j_epoch_[4];
   DevBuf<char> j_wide_train_[4], j_wide_eval_, j_wide_bwd_[4];   // wide path (k_wide.hip)
   DevBuf<char> j_rnn_mom_, j_mlp_mom_, j_wide_mom_;             // moment refresh (every split)
+  // moment LSTM jobs, one per job of j_rnn_train_ / j_rnn_eval_ / j_rnn_all_ / j_rnn_mom_ (same order)
+  DevBuf<char> j_ml_train_, j_ml_eval_, j_ml_all_, j_ml_mom_;
   DevBuf<char> j_mlp_bwd_dh_;                                   // moment backward from an external dL/dh
   DevBuf<char> j_loss_eval_dense_;                              // evaluation loss jobs, dense passes
   int n_mom_jobs_ = 0, tmax_all_ = 0, gx_mom_ = 1;
@@ -2009,7 +2037,7 @@ class Engine {
   // ------------------------------------------------------------ model descriptor ------
   void build_desc(int F, int M, int nrnn, int H, bool raw_macro_sdf, const std::vector<int>& hs,
                   const std::vector<int>& hm, int K, float dropout, bool normalize_w, bool weighted,
-                  float residual, bool fp32) {
+                  float residual, bool fp32, int mom_nrnn, int mom_H) {
     ModelDesc& d = md_;
     std::memset(&d, 0, sizeof d);
     if (hs.empty() || (int)hs.size() > 4) throw std::invalid_argument("native engine supports 1..4 SDF hidden layers");
@@ -2058,15 +2086,24 @@ class Engine {
     d.so_w = off; off += hs.back();
     d.so_b = off; off += 1;
     d.P_sdf = off;
+    // the moment network's own LSTM leads its segment (state_dict order: macro_lstm, fc_layers)
+    d.mnrnn = mom_nrnn; d.mH = mom_nrnn > 0 ? mom_H : 0;
+    if (d.mH > 0) {
+      d.mlstm_w_ih = off; off += 4 * d.mH * M;
+      d.mlstm_w_hh = off; off += 4 * d.mH * d.mH;
+      d.mlstm_b_ih = off; off += 4 * d.mH;
+      d.mlstm_b_hh = off; off += 4 * d.mH;
+    }
+    const int Mm = d.mH > 0 ? d.mH : M;           // width of the macro block of the moment input
     std::vector<int> mw(hm);
     mw.push_back(K);
     d.nl_m = (int)mw.size();
     int wmax = 0;
     for (int j = 0; j < d.nl_m; ++j) {
-      const int in = j == 0 ? M + F : mw[j - 1];
+      const int in = j == 0 ? Mm + F : mw[j - 1];
       PackLayer& L = d.m[j];
       L.w_off = off; L.b_off = off + mw[j] * in; L.out = mw[j];
-      L.in = j == 0 ? F : in; L.ld = in; L.col0 = j == 0 ? M : 0;
+      L.in = j == 0 ? F : in; L.ld = in; L.col0 = j == 0 ? Mm : 0;
       off += mw[j] * in + mw[j];
       wmax = std::max(wmax, mw[j]);
     }
@@ -2131,6 +2168,9 @@ class Engine {
     d.tps_m = 1;
     d.proj_mp = std::max(4, (M + 3) / 4 * 4);
     d.proj_np = ((nrnn > 0 ? 4 * H : 0) + 64 + 15) / 16 * 16;   // whole 16-wide MFMA tiles
+    // (moment LSTM: the table's 64 columns are not built -- launch_mlstm_fwd fills abias)
+    if (d.mH > 0) d.proj_np = std::max(16, ((nrnn > 0 ? 4 * H : 0) + 15) / 16 * 16);
+    if (d.mH > 0 && wide) throw std::logic_error("moment LSTM on the wide layer-0 path");   // (check_mom_lstm)
     for (int e = 0; e < SLAB_EXTRA; ++e) { d.extra_s[e] = -1; d.extra_m[e] = -1; }
     for (int j = 0; j < d.nl_s; ++j)
       for (int o = 0; o < d.s[j].out; ++o) d.extra_s[j * 64 + o] = d.s[j].b_off + o;
@@ -2170,6 +2210,13 @@ class Engine {
       W.gram.alloc((size_t)2 * T * T); W.gpart.alloc((size_t)2 * std::max(T, 1));
       W.xs.alloc((size_t)4 * T + 8);
       W.h0.alloc((size_t)std::max(md_.nrnn * H, 1)); W.c0.alloc((size_t)std::max(md_.nrnn * H, 1));
+      if (mlstm()) {
+        W.mxg.alloc((size_t)T * 4 * md_.mH); W.mhm.alloc((size_t)T * md_.mH);
+        if (s == 0) {
+          W.msg.alloc((size_t)T * 4 * md_.mH); W.msc.alloc((size_t)T * md_.mH);
+          W.mdg.alloc((size_t)T * 4 * md_.mH); W.mdhm.alloc((size_t)T * md_.mH);
+        }
+      }
       if (s == 0) { W.dh0.alloc((size_t)std::max(md_.nrnn * H, 1)); W.dc0.alloc((size_t)std::max(md_.nrnn * H, 1)); }
       if (s == 0) W.scal_prev.alloc(SC_NSCAL);
       if (md_.residual_factor > 0.f) W.rstat.alloc((size_t)T * 4);
@@ -2251,6 +2298,26 @@ class Engine {
     J.dropout = models_[g].dropout;
     if (s == 0 && train) J.prog = prog_ptr(g, 0);
     return J;
+  }
+  // moment LSTM job of (model, split); save: keep gates / cells for phase 2's backward (train split)
+  MlstmJob mlstm_job(int g, int s, bool save) {
+    ModelSplitWS& W = ws(g, s);
+    MlstmJob J{};
+    J.params = models_[g].params.p; J.grads = models_[g].grads.p;
+    J.macro = splits_[s].macro.p; J.T = splits_[s].T;
+    J.xg = W.mxg.p; J.hm = W.mhm.p; J.abias = W.abias.p;
+    if (save && s == 0) { J.sg = W.msg.p; J.sc = W.msc.p; }
+    if (s == 0) { J.dab = W.dab.p; J.dg = W.mdg.p; J.dhm = W.mdhm.p; }
+    return J;
+  }
+  // The per-period moment bias table of the jobs of an RnnJob table (same order and count). Without
+  // the moment LSTM k_proj builds it (the callers' abias flag); with it, launch_mlstm_fwd does, after
+  // that prologue on the same stream.
+  bool proj_abias(bool want) const { return want && !mlstm(); }
+  void mom_table(const DevBuf<char>& tab, int first, int njobs, int tmax, hipStream_t st, bool want, bool train) {
+    if (!want || !mlstm() || njobs <= 0) return;
+    HTRACE("launch_mlstm_fwd njobs=%d tmax=%d train=%d", njobs, tmax, (int)train);
+    launch_mlstm_fwd(as<MlstmJob>(tab) + first, njobs, tmax, dd(), md_, st, train);
   }
   // progress counter of the fused LSTM + tower forward of (model, split); set only on the job
   // tables that launch it (training split: train tables; evaluation splits: the eval tables)
@@ -2477,6 +2544,7 @@ class Engine {
       gx_bwd_ = nfine_ / fpw_;
     }
     std::vector<RnnJob> rt, re;
+    std::vector<MlstmJob> mlt, mle;
     std::vector<LossJob> le, led;
     std::vector<MlpJob> me;
     std::vector<FinJob> fj;
@@ -2485,9 +2553,11 @@ class Engine {
     n_eval_jobs_ = 0; tmax_eval_ = 0; nmax_eval_ = 0;
     for (int g = 0; g < G_; ++g) {
       rt.push_back(rnn_job(g, 0, true));
+      if (mlstm()) mlt.push_back(mlstm_job(g, 0, true));
       for (int s = 1; s < 3; ++s) {
         if (!splits_[s].set) continue;
         re.push_back(rnn_job(g, s, false));
+        if (mlstm()) mle.push_back(mlstm_job(g, s, false));
         me.push_back(mlp_job(g, s, false, true, !k_.h_cache));
         re.back().prog = prog_ptr(g, s);
         set_prog(me.back(), g, s);
@@ -2526,6 +2596,9 @@ class Engine {
       std::vector<RnnJob> ra = rt;
       ra.insert(ra.end(), re.begin(), re.end());
       upload(j_rnn_all_, ra);
+      std::vector<MlstmJob> ma = mlt;
+      ma.insert(ma.end(), mle.begin(), mle.end());
+      upload(j_ml_all_, ma); upload(j_ml_train_, mlt); upload(j_ml_eval_, mle);
     }
     {   // co-residency capacity of the fused launches (no GPU query when they cannot run)
       const int force = k_.fused_cap;
@@ -2544,6 +2617,7 @@ class Engine {
     upload(j_fin_, fj); upload(j_upd_, uj); upload(j_wide_eval_, we);
     {   // moment refresh: eval-mode moment tower (and its per-period bias) of every split
       std::vector<RnnJob> rm;
+      std::vector<MlstmJob> mlm;
       std::vector<MlpJob> mm;
       std::vector<WideJob> wm;
       // the train split's jobs first, then the evaluation splits' (ensure_moments may run the
@@ -2554,6 +2628,7 @@ class Engine {
           for (int s = grp ? 1 : 0; s < (grp ? 3 : 1); ++s) {
             if (!splits_[s].set) continue;
             rm.push_back(rnn_job(g, s, false));
+            if (mlstm()) mlm.push_back(mlstm_job(g, s, false));
             mm.push_back(mlp_job(g, s, false, false, true));
             wm.push_back(wide_job(g, s, false, true));
             tmax_all_ = std::max(tmax_all_, splits_[s].T);
@@ -2562,7 +2637,7 @@ class Engine {
             if (!grp) ++n_mom_tr_;
           }
       n_mom_jobs_ = (int)mm.size();
-      upload(j_rnn_mom_, rm); upload(j_mlp_mom_, mm); upload(j_wide_mom_, wm);
+      upload(j_rnn_mom_, rm); upload(j_mlp_mom_, mm); upload(j_wide_mom_, wm); upload(j_ml_mom_, mlm);
     }
     for (int phase = 1; phase <= 3; ++phase) {
       std::vector<MlpJob> mt, mb;
@@ -2645,18 +2720,21 @@ class Engine {
       // (DLAP_TRAIN_GRAM_SIDE: the train split's refresh and Gram build too, ahead of the evaluation
       // splits' -- the head epoch's forward needs neither, its loss pass waits, launch_head)
       hipStream_t sm = k_.train_gram_side ? st2_ : st_;
-      launch_prologue(as<RnnJob>(j_rnn_mom_), n_mom_tr_, tmax_mom_tr_, dd(), md_, sm, true, false);
+      launch_prologue(as<RnnJob>(j_rnn_mom_), n_mom_tr_, tmax_mom_tr_, dd(), md_, sm, proj_abias(true), false);
+      mom_table(j_ml_mom_, 0, n_mom_tr_, tmax_mom_tr_, sm, true, false);
       launch_mlp_fwd(as<MlpJob>(j_mlp_mom_), n_mom_tr_, gx_mom_, md_.md, md_.KS1, md_.WMB, sm);
       for (bool& v : gram_valid_) v = false;
       if (k_.train_gram_side) build_gram(gram_phase, true, 1);          // (the head's loss pass waits for it first)
-      launch_prologue(as<RnnJob>(j_rnn_mom_) + n_mom_tr_, n_ev, tmax_mom_ev_, dd(), md_, st2_, true, false);
+      launch_prologue(as<RnnJob>(j_rnn_mom_) + n_mom_tr_, n_ev, tmax_mom_ev_, dd(), md_, st2_, proj_abias(true), false);
+      mom_table(j_ml_mom_, n_mom_tr_, n_ev, tmax_mom_ev_, st2_, true, false);
       launch_mlp_fwd(as<MlpJob>(j_mlp_mom_) + n_mom_tr_, n_ev, gx_mom_, md_.md, md_.KS1, md_.WMB, st2_);
       h_valid_ = true;
       build_gram(gram_phase, true);
       return;
     }
     HTRACE("launch_prologue");
-    launch_prologue(as<RnnJob>(j_rnn_mom_), n_mom_jobs_, tmax_all_, dd(), md_, st_, true, false);
+    launch_prologue(as<RnnJob>(j_rnn_mom_), n_mom_jobs_, tmax_all_, dd(), md_, st_, proj_abias(true), false);
+    mom_table(j_ml_mom_, 0, n_mom_jobs_, tmax_all_, st_, true, false);
     if (md_.md.wide && k_.zx_eval) {
       HTRACE("launch_mlp_fwd_zx");
       launch_mlp_fwd_zx(as<MlpJob>(j_mlp_mom_), n_mom_jobs_, std::max(1, k_.zx_gx / n_mom_jobs_), md_.md, md_.WMB, st_);
@@ -2687,11 +2765,18 @@ class Engine {
     // (fused: only its input projection here, the recurrence runs inside the tower launch)
     const bool fused = P.fused_fwd, selfproj = P.selfproj && tp.own_proj;
     HTRACE("launch_prologue fused=%d eval_rnn=%d selfproj=%d", (int)fused, (int)tp.eval_rnn, (int)selfproj);
+    const bool tm = train_mom(phase);
     if (selfproj) {}
-    else if (tp.eval_rnn) launch_proj(as<RnnJob>(j_rnn_all_), G_ + n_eval_jobs_, tmax_fwd_all(), dd(), md_, st_, train_mom(phase));
-    else if (fused) launch_proj(as<RnnJob>(j_rnn_train_), G_, D.T, dd(), md_, st_, train_mom(phase));
-    else if (phase == 2 && tp.lstm_once) launch_prologue(as<RnnJob>(j_rnn_train_), G_, D.T, dd(), md_, st_, true, false);
-    else launch_prologue(as<RnnJob>(j_rnn_train_), G_, D.T, dd(), md_, st_, train_mom(phase));
+    else if (tp.eval_rnn) launch_proj(as<RnnJob>(j_rnn_all_), G_ + n_eval_jobs_, tmax_fwd_all(), dd(), md_, st_, proj_abias(tm));
+    else if (fused) launch_proj(as<RnnJob>(j_rnn_train_), G_, D.T, dd(), md_, st_, proj_abias(tm));
+    else if (phase == 2 && tp.lstm_once) launch_prologue(as<RnnJob>(j_rnn_train_), G_, D.T, dd(), md_, st_, proj_abias(true), false);
+    else launch_prologue(as<RnnJob>(j_rnn_train_), G_, D.T, dd(), md_, st_, proj_abias(tm));
+    // moment LSTM: the train split's table (phase 2: saving for the backward; the evaluation
+    // towers of an eval-in-forward launch run the SDF only or rebuild theirs in the eval branch)
+    if (!selfproj) {
+      if (tp.eval_rnn) mom_table(j_ml_all_, 0, G_ + n_eval_jobs_, tmax_fwd_all(), st_, tm, true);
+      else mom_table(j_ml_train_, 0, G_, D.T, st_, tm || (phase == 2 && tp.lstm_once), true);
+    }
     if (tp.eval_prologue) enqueue_eval_prologue(tp.eval_prologue, EvalPass());
     const bool zx_train = md_.md.wide && k_.zx_train;
     if (md_.md.wide && !zx_train)
@@ -2781,6 +2866,13 @@ class Engine {
     // sharded: the rank-local tower gradients and per-period input gradients (dpp, or phase 2's
     // dab) summed over the ranks before the replicated LSTM backward / moment macro columns
     xs_call("grads", phase, st_);
+    if (phase == 2 && mlstm()) {
+      // moment LSTM: dab goes back through the recurrence (db_m0, dW_m0[:, :Hm] and the LSTM
+      // tensors); the macro-column branch of k_lstm_bwd has no columns to fill
+      HTRACE("launch_mlstm_bwd");
+      launch_mlstm_bwd(as<MlstmJob>(j_ml_train_), G_, D.T, dd(), md_, st_);
+      return;
+    }
     HTRACE("launch_lstm_bwd");
     launch_lstm_bwd(as<UpdJob>(j_upd_), G_, dd(), md_, D.T, phase, st_);
   }
@@ -2800,8 +2892,9 @@ class Engine {
     if (n_eval_jobs_ == 0) return;
     HTRACE("launch_prologue");
     // fused: the input projections only, the recurrences run inside the tower launch
-    if (fused_eval(ep)) launch_proj(as<RnnJob>(j_rnn_eval_), n_eval_jobs_, tmax_eval_, dd(), md_, st, !k_.h_cache);
-    else launch_prologue(as<RnnJob>(j_rnn_eval_), n_eval_jobs_, tmax_eval_, dd(), md_, st, !k_.h_cache);
+    if (fused_eval(ep)) launch_proj(as<RnnJob>(j_rnn_eval_), n_eval_jobs_, tmax_eval_, dd(), md_, st, proj_abias(!k_.h_cache));
+    else launch_prologue(as<RnnJob>(j_rnn_eval_), n_eval_jobs_, tmax_eval_, dd(), md_, st, proj_abias(!k_.h_cache));
+    mom_table(j_ml_eval_, 0, n_eval_jobs_, tmax_eval_, st, !k_.h_cache, false);
   }
   void enqueue_eval_towers(hipStream_t st, const EvalPass& ep) {
     if (n_eval_jobs_ == 0) return;
@@ -2884,7 +2977,8 @@ class Engine {
       // the recurrences project their own inputs when the towers skip the moment network (cached
       // moments); else k_proj first (gate projections + the moment bias table)
       ep.selfproj = k_.self_proj && k_.h_cache;
-      if (!ep.selfproj) launch_proj(as<RnnJob>(j_rnn_eval_), n_eval_jobs_, tmax_eval_, dd(), md_, st2_, !k_.h_cache);
+      if (!ep.selfproj) launch_proj(as<RnnJob>(j_rnn_eval_), n_eval_jobs_, tmax_eval_, dd(), md_, st2_, proj_abias(!k_.h_cache));
+      mom_table(j_ml_eval_, 0, n_eval_jobs_, tmax_eval_, st2_, !k_.h_cache, false);
     } else {
       HTRACE("launch_wait_count");
       launch_wait_count(esync_.p, ne_per_model() * G_, k_.spin_limit, prog_.p, G_, st2_);
@@ -2994,14 +3088,16 @@ class Engine {
       std::vector<MlpJob> mj;
       std::vector<LossJob> lj;
       std::vector<WideJob> wj;
+      std::vector<MlstmJob> mlj;
       for (int g = 0; g < G_; ++g) {
         rj.push_back(rnn_job(g, s, train_mode, s == 0 ? 1 : 0));
+        if (mlstm()) mlj.push_back(mlstm_job(g, s, false));
         mj.push_back(mlp_job(g, s, train_mode, true, do_mom));
         lj.push_back(loss_job(g, s, 0));
         wj.push_back(wide_job(g, s, true, do_mom));
         if (!do_mom) lj.back().h = nullptr;
       }
-      upload(F.r, rj); upload(F.m, mj); upload(F.l, lj); upload(F.w, wj);
+      upload(F.r, rj); upload(F.m, mj); upload(F.l, lj); upload(F.w, wj); upload(F.ml, mlj);
       F.built = true;
     }
     return F;
@@ -3012,7 +3108,8 @@ class Engine {
     const SplitDev& D = splits_[s];
     const bool zx = md_.md.wide && k_.zx_eval && !train_mode;
     if (md_.md.wide && !zx) launch_proj0(as<WideJob>(F.w), G_, gx_proj_[s], md_.md, md_.WMB, st_);
-    launch_prologue(as<RnnJob>(F.r), G_, D.T, dd(), md_, st_, do_mom);
+    launch_prologue(as<RnnJob>(F.r), G_, D.T, dd(), md_, st_, proj_abias(do_mom));
+    mom_table(F.ml, 0, G_, D.T, st_, do_mom, false);
     if (zx) launch_mlp_fwd_zx(as<MlpJob>(F.m), G_, std::max(1, k_.zx_gx / G_), md_.md, md_.WMB, st_);
     else launch_mlp_fwd(as<MlpJob>(F.m), G_, gx_fwd_[s], md_.md, md_.KS1, md_.WMB, st_);
   }
@@ -3176,11 +3273,11 @@ PYBIND11_MODULE(_dlap_hip, m) {
   m.doc() = "DLAP MI355X native engine (HIP kernels for gfx950 + hipGraph epoch executor)";
   py::class_<Engine>(m, "Engine")
       .def(py::init<int, int, int, int, bool, std::vector<int>, std::vector<int>, int, float, bool, bool,
-                    float, int, int, bool>(),
+                    float, int, int, bool, int, int>(),
            py::arg("F"), py::arg("M"), py::arg("nrnn"), py::arg("H"), py::arg("raw_macro_sdf"),
            py::arg("hidden"), py::arg("mom_hidden"), py::arg("K"), py::arg("dropout"),
            py::arg("normalize_w"), py::arg("weighted"), py::arg("residual"), py::arg("G"),
-           py::arg("max_epochs"), py::arg("fp32") = false)
+           py::arg("max_epochs"), py::arg("fp32") = false, py::arg("mom_nrnn") = 0, py::arg("mom_H") = 0)
       .def("describe", &Engine::describe)
       .def("set_split", &Engine::set_split)
       .def("set_split_dev", &Engine::set_split_dev)

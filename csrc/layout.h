@@ -63,4 +63,9 @@ struct ModelDesc {
   int proj_mp, proj_np;
   GradTile tile_s[DLAP_MAX_TILES], tile_m[DLAP_MAX_TILES];
   int extra_s[SLAB_EXTRA], extra_m[SLAB_EXTRA];   // slab extra slot -> flat index (-1 unused)
+  // moment network's own macro LSTM (k_mlstm.hip; 0 / 0: none). Its four tensors lead the moment
+  // segment of the flat vector; m[0] then spans [hm ; x] (ld = mH + F, col0 = mH) and the moment
+  // columns of wproj are not built (launch_mlstm_fwd fills abias).
+  int mnrnn, mH;
+  int mlstm_w_ih, mlstm_w_hh, mlstm_b_ih, mlstm_b_hh;
 };

@@ -112,7 +112,9 @@ DLAP_HD float pack_proj_elem(const ModelDesc* __restrict__ md, PP P, int f) {
   const int G4 = md->nrnn > 0 ? 4 * md->H : 0;
   const PackLayer& L0 = md->m[0];
   const int om = o - G4;
-  if (m == md->proj_mp) {                       // bias rows: b_ih | b_m0, then b_hh | 0 (every
+  // moment LSTM: W_m0 has no macro columns (m[0] spans [hm ; x]) and the table is not k_proj's
+  if (md->mH > 0 && o >= G4) return 0.f;
+  if (m == md->proj_mp) {                      // bias rows: b_ih | b_m0, then b_hh | 0 (every
     if (o < G4) return P[md->lstm_b_ih[0] + o]; // packed element is one parameter, so the fused
     return om < md->cm1 ? P[L0.b_off + om] : 0.f;   // Adam can scatter each update itself)
   }

@@ -10,7 +10,9 @@ Quirks preserved on purpose:
   * the macro LSTM has ``len(num_units_rnn)`` layers, *all* of width ``num_units_rnn[-1]``
     (`model.py:39-45`);
   * ``num_units_rnn_moment`` / ``use_rnn_moment`` are parsed but have no effect
-    (`model.py:309-311,337-338`);
+    (`model.py:309-311,337-338`) -- unless the opt-in key ``moment_lstm`` is true, which
+    gives the moment network the paper's own macro LSTM of ``num_units_rnn_moment[-1]``
+    state variables (CSMV); with the key absent nothing changes;
   * the moment network input is ``[raw macro ; individual]`` while the SDF input is
     ``[individual ; lstm(macro)]`` (`model.py:253-255,513-516`).
 """
@@ -57,6 +59,8 @@ class ModelSpec:
     weighted_loss: bool
     residual_loss_factor: float
     raw: Dict = field(default_factory=dict, compare=False, hash=False)
+    moment_rnn_layers: int = 0   # moment-network LSTM layers (0 = none; opt-in ``moment_lstm``)
+    moment_rnn_hidden: int = 0   # width of every moment-LSTM layer
 
     @staticmethod
     def from_config(config: Dict) -> "ModelSpec":
@@ -65,6 +69,8 @@ class ModelSpec:
         use_rnn = bool(g("use_rnn"))
         macro_dim = int(g("macro_feature_dim"))
         has_lstm = use_rnn and len(rnn) > 0 and macro_dim > 0
+        rnn_m = _as_list(g("num_units_rnn_moment"))
+        has_mlstm = bool(config.get("moment_lstm", False)) and len(rnn_m) > 0 and macro_dim > 0
         return ModelSpec(
             macro_dim=macro_dim,
             individual_dim=int(config["individual_feature_dim"]),
@@ -78,6 +84,8 @@ class ModelSpec:
             weighted_loss=bool(g("weighted_loss")),
             residual_loss_factor=float(g("residual_loss_factor")),
             raw=dict(config),
+            moment_rnn_layers=len(rnn_m) if has_mlstm else 0,
+            moment_rnn_hidden=rnn_m[-1] if has_mlstm else 0,
         )
 
     # ---- derived dimensions -------------------------------------------------------
@@ -92,7 +100,7 @@ class ModelSpec:
 
     @property
     def moment_in(self) -> int:
-        return self.macro_dim + self.individual_dim
+        return (self.moment_rnn_hidden or self.macro_dim) + self.individual_dim
 
     def param_layout(self) -> List[Tuple[str, Tuple[int, ...]]]:
         """(state_dict key, shape) in ``state_dict()`` order of the reference module."""
@@ -109,6 +117,12 @@ class ModelSpec:
                     (f"sdf_net.fc_layers.{3 * j}.bias", (h,))]
             prev = h
         out += [("sdf_net.output_proj.weight", (1, prev)), ("sdf_net.output_proj.bias", (1,))]
+        Hm = self.moment_rnn_hidden
+        for l in range(self.moment_rnn_layers):
+            inp = self.macro_dim if l == 0 else Hm
+            p = "moment_net.macro_lstm.lstm."
+            out += [(f"{p}weight_ih_l{l}", (4 * Hm, inp)), (f"{p}weight_hh_l{l}", (4 * Hm, Hm)),
+                    (f"{p}bias_ih_l{l}", (4 * Hm,)), (f"{p}bias_hh_l{l}", (4 * Hm,))]
         prev = self.moment_in
         for j, h in enumerate(self.moment_hidden):
             out += [(f"moment_net.fc_layers.{3 * j}.weight", (h, prev)),
@@ -134,10 +148,12 @@ class ModelSpec:
 
 def default_cli_config(macro_dim: int, individual_dim: int, hidden_dim=(64, 64), use_lstm=True,
                        rnn_dim=(4,), num_moments=8, dropout=0.05, hidden_dim_moment=(),
-                       rnn_dim_moment=(32,)) -> Dict:
-    """The 17-key dict the CLI writes to ``config.json`` (`/root/reference/src/train.py:530-561`)."""
+                       rnn_dim_moment=(32,), moment_lstm=False) -> Dict:
+    """The 17-key dict the CLI writes to ``config.json`` (`/root/reference/src/train.py:530-561`);
+    ``moment_lstm=True`` adds that opt-in key."""
     hidden_dim, rnn_dim = list(hidden_dim), list(rnn_dim)
     hidden_dim_moment, rnn_dim_moment = list(hidden_dim_moment), list(rnn_dim_moment)
+    extra = {"moment_lstm": True} if moment_lstm else {}
     return {
         "macro_feature_dim": macro_dim,
         "individual_feature_dim": individual_dim,
@@ -158,4 +174,5 @@ def default_cli_config(macro_dim: int, individual_dim: int, hidden_dim=(64, 64),
         "normalize_w": True,
         "weighted_loss": True,
         "residual_loss_factor": 0.0,
+        **extra,
     }

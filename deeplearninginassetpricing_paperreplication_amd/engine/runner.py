@@ -86,7 +86,8 @@ class GANEngine:
             raw_macro_sdf=(spec.rnn_layers == 0 and spec.macro_dim > 0),
             hidden=list(spec.hidden), mom_hidden=list(spec.moment_hidden), K=spec.num_moments,
             dropout=spec.dropout, normalize_w=spec.normalize_w, weighted=spec.weighted_loss,
-            residual=spec.residual_loss_factor, G=n_models, max_epochs=max_epochs, fp32=self.fp32)
+            residual=spec.residual_loss_factor, G=n_models, max_epochs=max_epochs, fp32=self.fp32,
+            mom_nrnn=spec.moment_rnn_layers, mom_H=spec.moment_rnn_hidden)
         self.desc = self.eng.describe()
         self.KP = int(self.desc["KP"])
         self.splits: Dict[int, object] = {}

@@ -7,7 +7,9 @@ shapes and the default-initialisation RNG stream are identical for a given torch
 Execution: on CPU the forward is the vectorised fp32 math of ``models.losses`` (the
 semantic oracle).  On a GPU device the whole ``AssetPricingGAN.forward`` / ``get_weights``
 runs through the native HIP engine (``ops.fused``): fused MFMA MLP, fused masked
-E[h·w·R]² reductions and the persistent LSTM kernel — never eager PyTorch.
+E[h·w·R]² reductions and the persistent LSTM kernel — never eager PyTorch. The one exception is
+a model with the opt-in moment LSTM (config key ``moment_lstm``): its training runs on the engine
+(``engine.runner``), its module-level forward on CUDA tensors runs the torch ops.
 """
 from __future__ import annotations
 
@@ -56,18 +58,31 @@ class MomentNetwork(nn.Module):
     """Discriminator h = tanh(FFN([macro ; x])) → [K, T, N].
 
     ``use_rnn`` / ``rnn_hidden_dims`` are accepted and ignored, as in the reference
-    (`model.py:99-130`).
+    (`model.py:99-130`).  With ``macro_lstm_dim > 0`` (config key ``moment_lstm``) the
+    network owns the paper's macro LSTM: ``encode_macro`` maps the split's [T, M] series to
+    the [T, Hm] state that replaces the raw macro block of the input.  Its state starts
+    from zero on every call.
     """
 
     def __init__(self, input_dim: int, hidden_dims: List[int], num_moments: int,
-                 use_rnn: bool = False, rnn_hidden_dims: List[int] = None, dropout: float = 0.05):
+                 use_rnn: bool = False, rnn_hidden_dims: List[int] = None, dropout: float = 0.05,
+                 macro_lstm_dim: int = 0):
         super().__init__()
         self.use_rnn = use_rnn
         self.num_moments = num_moments
+        if macro_lstm_dim > 0:      # registered before fc_layers, as SDFNetwork does
+            self.macro_lstm = MacroLSTM(macro_lstm_dim, rnn_hidden_dims, dropout)
+        else:
+            self.macro_lstm = None
         layers = _mlp(input_dim, list(hidden_dims), dropout)
         self.fc_layers = nn.Sequential(*layers) if layers else nn.Identity()
         last = hidden_dims[-1] if len(hidden_dims) else input_dim
         self.output_proj = nn.Linear(last, num_moments)
+
+    def encode_macro(self, macro):
+        if macro is None or self.macro_lstm is None:
+            return macro
+        return self.macro_lstm(macro)[0]
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         T, N, D = x.shape
@@ -141,7 +156,9 @@ class AssetPricingGAN(nn.Module):
         self.moment_net = MomentNetwork(
             input_dim=spec.moment_in, hidden_dims=list(spec.moment_hidden),
             num_moments=spec.num_moments, use_rnn=use_rnn_m,
-            rnn_hidden_dims=rnn_m if use_rnn_m else None, dropout=spec.dropout)
+            rnn_hidden_dims=rnn_m if (use_rnn_m or spec.moment_rnn_layers) else None,
+            dropout=spec.dropout,
+            macro_lstm_dim=spec.macro_dim if spec.moment_rnn_layers > 0 else 0)
         self.residual_loss_factor = spec.residual_loss_factor
         self.weighted_loss = spec.weighted_loss
 
@@ -158,6 +175,7 @@ class AssetPricingGAN(nn.Module):
     def _moment_input(self, macro, individual):
         if macro is None:
             return individual
+        macro = self.moment_net.encode_macro(macro)
         T, N, _ = individual.shape
         return torch.cat([macro[:, None, :].expand(T, N, macro.shape[-1]), individual], -1)
 
@@ -166,6 +184,11 @@ class AssetPricingGAN(nn.Module):
         if individual_features.is_cuda:
             from ..ops.fused import gan_forward
             return gan_forward(self, macro_features, individual_features, returns, mask, phase, hidden)
+        return self._forward_eager(macro_features, individual_features, returns, mask, hidden, phase)
+
+    def _forward_eager(self, macro_features, individual_features, returns, mask, hidden=None,
+                       phase: str = "conditional") -> Dict[str, torch.Tensor]:
+        """The torch forward (the CPU oracle; any device)."""
         weights, new_hidden = self.sdf_net(macro_features, individual_features, mask, hidden)
         moments = self.moment_net(self._moment_input(macro_features, individual_features))
         zero = torch.zeros((), device=weights.device)
@@ -196,6 +219,10 @@ class AssetPricingGAN(nn.Module):
         if individual_features.is_cuda:
             from ..ops.fused import gan_weights
             return gan_weights(self, macro_features, individual_features, mask, normalized, hidden)
+        return self._weights_eager(macro_features, individual_features, mask, hidden, normalized)
+
+    def _weights_eager(self, macro_features, individual_features, mask, hidden=None,
+                       normalized: bool = False):
         w, new_hidden = self.sdf_net(macro_features, individual_features, mask, hidden)
         if normalized:
             w = L.l1_normalize(w, mask)

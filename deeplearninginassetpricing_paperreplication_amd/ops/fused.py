@@ -375,9 +375,26 @@ def _masked_moments(model, s: _Slot, h: torch.Tensor, macro, individual) -> torc
     return flat.reshape(T, N, K).permute(2, 0, 1)
 
 
+_EAGER_NOTE = {"printed": False}
+
+
+def _moment_lstm_eager(spec) -> bool:
+    """A model with the moment LSTM (config key ``moment_lstm``) has no module-level engine path:
+    its forward on CUDA tensors runs the torch ops of ``AssetPricingGAN._forward_eager`` (training
+    on the GPU goes through ``GANEngine``). One note per process."""
+    if spec.moment_rnn_layers == 0:
+        return False
+    if not _EAGER_NOTE["printed"]:
+        _EAGER_NOTE["printed"] = True
+        print("note: moment_lstm model: module-level forward on CUDA tensors runs the torch ops (no engine)")
+    return True
+
+
 def gan_forward(model, macro, individual, returns, mask, phase: str = "conditional", hidden=None) -> Dict:
     if phase not in _PHASE:
         raise ValueError(f"unknown phase {phase!r}")
+    if _moment_lstm_eager(model.spec):
+        return model._forward_eager(macro, individual, returns, mask, hidden, phase)
     dev = individual.device
     spec = model.spec
     params = _ordered_params(model)
@@ -457,6 +474,8 @@ def gan_weights(model, macro, individual, mask, normalized: bool = False, hidden
     in the SDF parameters (and in ``hidden``) when grad mode is on."""
     # get_weights has no returns argument: a cached zero panel keeps the upload cache valid
     spec = model.spec
+    if _moment_lstm_eager(spec):
+        return model._weights_eager(macro, individual, mask, hidden, normalized)
     params = _ordered_params(model)
     if hidden is not None and (spec.rnn_layers == 0 or macro is None):
         hidden = None

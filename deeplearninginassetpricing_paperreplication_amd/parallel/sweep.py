@@ -5,7 +5,9 @@ Grid (paper Table A.VIII):
     HL  {2,3,4}        SDF hidden layers of 64 units        -> hidden_dim = [64] * HL
     SMV {4,8}          macro LSTM states                    -> num_units_rnn = [SMV]
     CSMV {16,32}       conditional-network macro states     -> num_units_rnn_moment = [CSMV]
-                       (accepted and ignored by the model, exactly as in the reference)
+                       (accepted and ignored by the model, exactly as in the reference, unless
+                       ``--moment_lstm`` sets the opt-in key ``moment_lstm`` on every config:
+                       CSMV is then the width of the moment network's own macro LSTM)
     CHL {0,1}          conditional hidden layers            -> hidden_dim_moment = [] | [CHU]
     CHU {4,8,16,32}    conditional units (moment count)     -> num_condition_moment = CHU
     LR  {1e-3,5e-4,2e-4,1e-4}
@@ -22,7 +24,8 @@ num_moments, with SMV doubling it to 384): HL {2,3,4} x LR {4 values} x dropout 
 Execution: configurations that build the same network form a *bucket* (LR, dropout and the
 no-op CSMV vary inside it); a bucket is trained as ONE batched native-engine run, one member per
 config (per-member learning rates and dropout rates, ``Engine.set_lr`` / ``Engine.set_dropout``),
-so the paper grid's 384 configs are 48 engine runs and the baseline grid's 24 runs of 16. Buckets are assigned to ranks longest-processing-time first (``comm.assign_lpt``) by
+so the paper grid's 384 configs are 48 engine runs (96 runs of 4 with ``--moment_lstm``, where CSMV
+changes the network) and the baseline grid's 24 runs of 16. Buckets are assigned to ranks longest-processing-time first (``comm.assign_lpt``) by
 ``bucket_cost``: the measured per-epoch time of that architecture's 8-member engine on the
 600 x 3000 panel (``sweep_costs.json``, written by ``tools/sweep_costs.py`` on an MI355X) or,
 for architectures it does not list, an analytic estimate. A bucket that raises marks its
@@ -56,10 +59,11 @@ METRICS = ("ok", "valid_sharpe", "test_sharpe", "train_sharpe", "valid_loss", "t
 
 
 def paper_grid(M: int, F: int, grid: Dict = GRID, dropout: float = 0.05,
-               chu: str = "both") -> List[Tuple[Dict, float, Dict]]:
+               chu: str = "both", moment_lstm: bool = False) -> List[Tuple[Dict, float, Dict]]:
     """[(model config, lr, grid point)] in a fixed order (384 entries for the paper grid).
     ``chu``: "both" -- CHU is the moment count and the conditional hidden width; "hidden" --
-    8 moments, CHU only the conditional hidden width."""
+    8 moments, CHU only the conditional hidden width. ``moment_lstm``: set the opt-in key on every
+    config (CSMV then is the moment LSTM's width and changes the architecture)."""
     keys = list(grid)
     out = []
     for vals in itertools.product(*(grid[k] for k in keys)):
@@ -67,7 +71,8 @@ def paper_grid(M: int, F: int, grid: Dict = GRID, dropout: float = 0.05,
         k = pt["CHU"] if chu == "both" else 8
         cfg = default_cli_config(M, F, hidden_dim=[64] * pt["HL"], rnn_dim=[pt["SMV"]],
                                  num_moments=k, dropout=dropout,
-                                 hidden_dim_moment=[pt["CHU"]] * pt["CHL"], rnn_dim_moment=[pt["CSMV"]])
+                                 hidden_dim_moment=[pt["CHU"]] * pt["CHL"], rnn_dim_moment=[pt["CSMV"]],
+                                 moment_lstm=moment_lstm)
         out.append((cfg, float(pt["LR"]), pt))
     return out
 
@@ -85,8 +90,10 @@ def baseline_grid(M: int, F: int, grid: Dict = BASELINE_GRID) -> List[Tuple[Dict
 
 
 def arch_key(spec: ModelSpec) -> str:
-    """Cost-table key of an architecture: SDF depth, LSTM width, moment hidden widths, moments."""
-    return f"HL{len(spec.hidden)}-H{spec.rnn_hidden}-CH{'x'.join(map(str, spec.moment_hidden)) or 0}-K{spec.num_moments}"
+    """Cost-table key of an architecture: SDF depth, LSTM width, moment hidden widths, moments
+    (and ``-ML{Hm}`` only for a model with the moment LSTM, so the keys of all others stay)."""
+    key = f"HL{len(spec.hidden)}-H{spec.rnn_hidden}-CH{'x'.join(map(str, spec.moment_hidden)) or 0}-K{spec.num_moments}"
+    return key + (f"-ML{spec.moment_rnn_hidden}" if spec.moment_rnn_layers > 0 else "")
 
 
 def _load_costs() -> Dict[str, float]:
@@ -115,6 +122,11 @@ def bucket_cost(spec: ModelSpec, members: int = 8, table: Optional[Dict[str, flo
     sdf = 0.45 * hl * (1.6 if hl >= 3 else 1.0)
     mom = 0.12 * wmb * (1 + len(spec.moment_hidden))
     serial = 0.5 + (0.1 if spec.rnn_hidden > 4 else 0.0)
+    if spec.moment_rnn_layers > 0:
+        # the moment recurrence and its BPTT are serial over the periods in phase 2 (one workgroup
+        # per member, so it does not grow with the members) and once per refresh elsewhere; phase 2
+        # is ~1/20 of a schedule's epochs
+        serial += 0.05 + 0.05 * spec.moment_rnn_hidden / 32.0
     return (serial + (sdf + mom) * members / 8.0)
 
 
@@ -125,7 +137,8 @@ def buckets(entries: Sequence[Tuple[Dict, float, Dict]]) -> List[List[int]]:
     differ only in lr, in dropout (a per-member rate of the batched engine) or in keys the model
     ignores -- CSMV (``num_units_rnn_moment``) is such a no-op in the reference
     (`/root/reference/src/model.py:309-311`) -- share a bucket: the paper grid's 384 configs
-    are 48 architectures x 8 members, the baseline grid's 24 x 16.
+    are 48 architectures x 8 members, the baseline grid's 24 x 16. With the opt-in key
+    ``moment_lstm`` CSMV is the moment LSTM's width, part of the spec: 96 architectures x 4.
 
     With hidden moment layers the engine's structural switch "the train split's moments can be
     cached in phase 3" depends on whether ANY batched member drops out (their keep masks change
@@ -314,6 +327,8 @@ def main(argv=None):
     p.add_argument("--chu", choices=["both", "hidden"], default="both",
                    help="paper grid: CHU sets the moment count and hidden width (both) or the hidden width only")
     p.add_argument("--balance", choices=["lpt", "round_robin"], default="lpt")
+    p.add_argument("--moment_lstm", action="store_true",
+                   help="paper grid: give the moment network its own macro LSTM of CSMV states (96 buckets of 4)")
     a = p.parse_args(argv)
     if not a.synthetic and not a.data_dir:
         p.error("--data_dir or --synthetic is required")
@@ -321,7 +336,7 @@ def main(argv=None):
     batches = load_batches(a, d)
     M = batches["train"]["macro_features"].shape[-1] if "macro_features" in batches["train"] else 0
     F = batches["train"]["individual_features"].shape[-1]
-    entries = paper_grid(M, F, chu=a.chu) if a.grid == "paper" else baseline_grid(M, F)
+    entries = paper_grid(M, F, chu=a.chu, moment_lstm=a.moment_lstm) if a.grid == "paper" else baseline_grid(M, F)
     if a.limit:
         entries = entries[:a.limit]
     res = run_sweep(batches, entries, d, (a.epochs_unc, a.epochs_moment, a.epochs), a.ignore_epoch, a.seed,

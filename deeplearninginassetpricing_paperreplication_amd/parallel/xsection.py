@@ -52,6 +52,7 @@ import numpy as np
 import torch
 import torch.distributed as tdist
 
+from ..config import ModelSpec
 from ..models import losses as L
 from ..models.gan import AssetPricingGAN
 from ..train.metrics import compute_max_drawdown, compute_sharpe
@@ -102,6 +103,15 @@ def _mkey(t: torch.Tensor):
     return (t.data_ptr(), tuple(t.shape), t._version)
 
 
+def _no_moment_lstm(spec) -> None:
+    """The sharded engine paths hand external gradients to the engine (``set_xs`` /
+    ``xs_backward``), which the moment LSTM's backward does not take."""
+    if spec.moment_rnn_layers > 0:
+        raise NotImplementedError(
+            "cross-sectional sharding on the native engine does not support moment_lstm "
+            "(the moment network's own macro LSTM); train it unsharded or on the torch path")
+
+
 class EngineTowers:
     """The rank's local towers on the native engine (one model, the rank's shards of the
     train / valid / test splits). Reference modules: `SDFNetwork` / `MomentNetwork` /
@@ -112,6 +122,7 @@ class EngineTowers:
         from ..engine.runner import GANEngine
         self.device = torch.device(device)
         self.spec = model.spec
+        _no_moment_lstm(self.spec)
         self.eng = GANEngine(model.spec, 1, max_epochs=8, precision=precision)
         dev = [None if b is None else {k: (v.to(self.device) if isinstance(v, torch.Tensor) else v)
                                        for k, v in b.items() if k != "n_total"} for b in shards]
@@ -731,6 +742,7 @@ def train_3phase_xsection_engine(config: Dict, train_data: Dict, valid_data: Dic
     (the weights are the rank's stocks). ``kw``: the schedule / optimiser arguments of
     ``engine.runner.train_3phase_gpu``."""
     from ..engine.runner import train_3phase_gpu
+    _no_moment_lstm(ModelSpec.from_config(config))
     device = torch.device(device or dist.device)
     sh = [None if b is None else (b if "n_total" in b else shard_batch(b, dist.rank, dist.world))
           for b in (train_data, valid_data, test_data)]

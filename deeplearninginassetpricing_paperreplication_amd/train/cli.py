@@ -15,7 +15,7 @@ from pathlib import Path
 import numpy as np
 import torch
 
-from ..config import default_cli_config
+from ..config import ModelSpec, default_cli_config
 from ..data.dataset import AssetPricingDataset, create_small_sample
 from .trainer import save_history, train_3phase
 
@@ -43,6 +43,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--dropout", type=float, default=0.05)
     p.add_argument("--hidden_dim_moment", type=int, nargs="+", default=[])
     p.add_argument("--rnn_dim_moment", type=int, nargs="+", default=[32])
+    p.add_argument("--moment_lstm", action="store_true",
+                   help="give the moment network its own macro LSTM of --rnn_dim_moment states (paper CSMV)")
     p.add_argument("--seed", type=int, default=42)
     # additions
     p.add_argument("--device", type=str, default=None, help="cpu | cuda[:k] (default: auto)")
@@ -91,12 +93,15 @@ def main(argv=None):
     else:
         config = default_cli_config(tr.macro_feature_dim, tr.individual_feature_dim,
                                     args.hidden_dim, args.use_lstm, args.rnn_dim, args.num_moments,
-                                    args.dropout, args.hidden_dim_moment, args.rnn_dim_moment)
+                                    args.dropout, args.hidden_dim_moment, args.rnn_dim_moment,
+                                    moment_lstm=args.moment_lstm)
     print("\nModel Configuration (matching paper):")
     print(f"  SDF hidden dims: {config['hidden_dim']}")
     print(f"  SDF LSTM: {config['use_rnn']} with units {config.get('num_units_rnn', [])}")
     print(f"  Moment hidden dims: {config['hidden_dim_moment']}")
-    print(f"  Moment LSTM: {config.get('use_rnn_moment', False)} with units {config.get('num_units_rnn_moment', [])}")
+    mspec = ModelSpec.from_config(config)
+    print(f"  Moment LSTM: {mspec.moment_rnn_layers > 0} with units "
+          f"{[mspec.moment_rnn_hidden] * mspec.moment_rnn_layers}")
     print(f"  Num moments: {config['num_condition_moment']}")
     print(f"  Dropout: {config['dropout']} (keep prob: {1 - config['dropout']:.2f})")
     print(f"\nTraining Configuration:\n  Phase 1 (unconditional): {args.epochs_unc} epochs\n"
