@@ -2526,7 +2526,7 @@ class Engine {
       HIP_LEGACY(hipMemset(S.tail_ctr.p, 0, S.tail_ctr.n * sizeof(int)));
       HIP_LEGACY(hipMemset(S.upd_ctr.p, 0, S.upd_ctr.n * sizeof(int)));
     }
-    tail_cap_ = splits_[0].set && lstm_tail_supported(md_, splits_[0].T) ? lstm_tail_capacity(md_, splits_[0].T) : 0;
+    tail_cap_ = splits_[0].set && lstm_tail_supported(md_, splits_[0].T) ? lstm_tail_capacity(md_, splits_[0].T, G_) : 0;
     for (auto& kv : graphs_) retire_graph_exec(kv.second, st_);
     graphs_.clear();
     fwd_tables_.clear();

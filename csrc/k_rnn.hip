@@ -1238,15 +1238,22 @@ DLAP_DEV void tail_adam(const UpdJob& U, const ModelDesc* __restrict__ md, float
 // blocks sum the weight-gradient slabs; the next (M + 16) / 16 blocks wait for block 0's gate
 // gradients and form the layer-0 W_ih gradient (wgrad_block) while block 0 forms W_hh and the
 // biases. Every block runs the same arithmetic as the separate kernels, so the results are
-// bitwise equal. Blocks 0 and the W_ih blocks wait only for blocks that never wait, and the
-// launch (under 400 blocks per model at the bench size) is resident at once on an idle device.
+// bitwise equal. Blocks 0 and the W_ih blocks wait only for lower-numbered blocks that never
+// wait, so the launch (under 400 blocks per model at the bench size) need not be resident at once
+// (it is at two workgroups per CU on an idle device; the one-model build below holds one per CU).
 // ljobs (optional): the train split's loss jobs of the step -- one more block per model computes
 // its job metrics (k_job_metrics' body; the loss passes finished before this launch), so the
 // pipelined epoch needs no fork to the evaluation branch for them.
 // adam (tail_adam): the clip + Adam update of the step in the launch's last blocks (2: after
 // the evaluation branch's signal; the only mode).
-template <int HM>
-__global__ __launch_bounds__(256, 2) void k_lstm_tail(const UpdJob* __restrict__ ujobs, const FinJob* __restrict__ fjobs,
+// WPS (waves per SIMD the register budget is set for): 2 keeps two workgroups on a CU, but at
+// LSTM width 4 the dense-state BPTT of block 0 then spills (432 bytes of scratch per thread, on
+// the serial path: BPTT 18.5 -> 16.5 us without). One model per launch has under 400 workgroups
+// for 256 CUs and is bound by block 0, so it runs the WPS = 1 build (368 registers, no scratch);
+// batched models need the slots (nine models: 0.683 -> 0.702 ms per epoch at WPS = 1) and keep 2.
+// Same arithmetic either way: the bits do not depend on the batch size.
+template <int HM, int WPS>
+__global__ __launch_bounds__(256, WPS) void k_lstm_tail(const UpdJob* __restrict__ ujobs, const FinJob* __restrict__ fjobs,
                                                    const ModelDesc* __restrict__ md, int slab_stride, int nslab_blocks,
                                                    const LossJob* __restrict__ ljobs, int adam, float lr, int phase) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
@@ -1350,11 +1357,14 @@ static size_t tail_dyn_lds(const ModelDesc& mh, int T, int phase = 1) {
 bool mom_tail_supported(const ModelDesc& mh, int T) {
   return mh.M > 0 && mh.m[0].out <= 64 && T >= 1;
 }
-int lstm_tail_capacity(const ModelDesc& mh, int T) {
+// the build a launch over njobs models runs (k_lstm_tail: WPS)
+static bool tail_one_wave(const ModelDesc& mh, int njobs) { return mh.H <= 4 && njobs == 1; }
+int lstm_tail_capacity(const ModelDesc& mh, int T, int njobs) {
   const size_t sh = tail_dyn_lds(mh, T);
   int per_cu = 0, dev = 0, ncu = 0;
-  if (mh.H <= 4) HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_lstm_tail<4>, 256, sh));
-  else HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_lstm_tail<8>, 256, sh));
+  if (tail_one_wave(mh, njobs)) HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_lstm_tail<4, 1>, 256, sh));
+  else if (mh.H <= 4) HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_lstm_tail<4, 2>, 256, sh));
+  else HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_lstm_tail<8, 2>, 256, sh));
   HIP_OK(hipGetDevice(&dev));
   HIP_OK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
   return per_cu * ncu;
@@ -1365,12 +1375,15 @@ void launch_lstm_tail(const UpdJob* ujobs, const FinJob* fjobs, int njobs, const
   const int nwg = (mh.M + 1 + 15) / 16;
   const size_t sh = tail_dyn_lds(mh, T, phase);
   const dim3 grid(1 + T + nslab_blocks + nwg + (ljobs ? 1 : 0), njobs);
-  if (mh.H <= 4)
-    hipLaunchKernelGGL(k_lstm_tail<4>, grid, dim3(256), sh, st, ujobs, fjobs, md, slab_stride, nslab_blocks, ljobs, adam, lr,
-                       phase);
+  if (tail_one_wave(mh, njobs))
+    hipLaunchKernelGGL((k_lstm_tail<4, 1>), grid, dim3(256), sh, st, ujobs, fjobs, md, slab_stride, nslab_blocks, ljobs, adam,
+                       lr, phase);
+  else if (mh.H <= 4)
+    hipLaunchKernelGGL((k_lstm_tail<4, 2>), grid, dim3(256), sh, st, ujobs, fjobs, md, slab_stride, nslab_blocks, ljobs, adam,
+                       lr, phase);
   else
-    hipLaunchKernelGGL(k_lstm_tail<8>, grid, dim3(256), sh, st, ujobs, fjobs, md, slab_stride, nslab_blocks, ljobs, adam, lr,
-                       phase);
+    hipLaunchKernelGGL((k_lstm_tail<8, 2>), grid, dim3(256), sh, st, ujobs, fjobs, md, slab_stride, nslab_blocks, ljobs, adam,
+                       lr, phase);
   HIP_OK(hipGetLastError());
 }
 

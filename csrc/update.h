@@ -114,7 +114,7 @@ void launch_lstm_bwd(const UpdJob* jobs, int njobs, const ModelDesc* md, const M
 bool lstm_tail_supported(const ModelDesc& mh, int T);
 int lstm_tail_words();     // ints of UpdJob::tail_ctr (hand-off words, 128 bytes apart)
 // workgroups of k_lstm_tail the device holds at once (occupancy query x CUs) at split length T
-int lstm_tail_capacity(const ModelDesc& mh, int T);
+int lstm_tail_capacity(const ModelDesc& mh, int T, int njobs);   // (of the build a launch over njobs models runs)
 struct LossJob;
 // ljobs: the train split's loss jobs whose job metrics one more block per model computes (or nullptr)
 // adam: 0 = none (k_adam follows); 2 = the update runs in the tail (the launch's last blocks,

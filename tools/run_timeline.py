@@ -33,7 +33,8 @@ def main():
     for r in rows:
         r["Kernel_Name"] = dm[r["Kernel_Name"]]
     rows.sort(key=lambda r: int(r["Start_Timestamp"]))
-    idx = [i for i, r in enumerate(rows) if r["Kernel_Name"].startswith(a.marker)]
+    # (a template kernel demangles to "void k_lstm_tail<4>(...)": match the name before its arguments)
+    idx = [i for i, r in enumerate(rows) if a.marker in r["Kernel_Name"].split("(")[0]]
     lo = idx[-a.adams - 1] if len(idx) > a.adams else 0
     sel = rows[lo:]
     t0 = int(sel[0]["Start_Timestamp"])
