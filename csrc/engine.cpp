@@ -145,6 +145,39 @@ struct DevBuf {
   ~DevBuf() { free(); }
 };
 
+// GPU time of an analysis pass: `marks` events, recorded in order on the engine stream around the
+// launches; after the caller's sync, ms(i) is the time between marks i and i + 1. The events are
+// destroyed on every way out, a launcher that throws on its arguments included.
+class GpuTimer {
+  struct Event {
+    hipEvent_t e = nullptr;
+    Event() { HIP_OK(hipEventCreate(&e)); }
+    Event(const Event&) = delete;
+    Event& operator=(const Event&) = delete;
+    ~Event() { (void)hipEventDestroy(e); }
+  };
+  std::vector<Event> ev_;                    // (a constructor that throws destroys the events before it)
+  hipStream_t st_;
+  size_t next_ = 0;
+
+ public:
+  explicit GpuTimer(hipStream_t st, int marks = 2) : ev_((size_t)marks), st_(st) {}
+  void mark() { HIP_OK(hipEventRecord(ev_.at(next_++).e, st_)); }
+  float ms(int i = 0) const {
+    float v = 0.f;
+    HIP_OK(hipEventElapsedTime(&v, ev_.at(i).e, ev_.at(i + 1).e));
+    return v;
+  }
+};
+
+// A result array of an analysis pass, filled with what an empty split or period reports
+template <typename T>
+py::array_t<T> filled(std::vector<py::ssize_t> shape, T v) {
+  py::array_t<T> a(std::move(shape));
+  std::fill_n(a.mutable_data(), a.size(), v);
+  return a;
+}
+
 struct SplitDev {
   int T = 0, N = 0, R = 0;
   float Nbar = 0.f;
@@ -766,10 +799,9 @@ class Engine {
   // the per-period inputs); false when the caller has just done so (forward_split(s, false, ...)).
   bool sens_ok() const { return sens_supported(md_.md, md_.KS1); }
   py::dict input_sensitivity(int s, uintptr_t scale, bool refresh = true) {
-    if (s < 0 || s > 2) throw std::invalid_argument("split must be 0, 1 or 2");
+    check_split(s, "input_sensitivity", kSplitIndex);
     ensure_jobs();
-    const SplitDev& D = splits_[s];
-    if (!D.set) throw std::runtime_error("split not set");
+    const SplitDev& D = check_split(s, "input_sensitivity", kSplitSet);
     if (!sens_supported(md_.md, md_.KS1))
       throw std::invalid_argument("input_sensitivity: not available for this shape (wide layer-0 path, or the "
                                   "fragments exceed the LDS budget)");
@@ -782,30 +814,14 @@ class Engine {
       DevBuf<char> tj, tsj;
       DevBuf<float> scl, part;
       DevBuf<double> res;
-      const size_t ns = (size_t)G_ * D.T;
-      scl.alloc(ns, false);
-      if (scale) {
-        HIP_OK(hipMemcpyAsync(scl.p, reinterpret_cast<const void*>(scale), ns * sizeof(float),
-                              hipMemcpyDeviceToDevice, st_));
-      } else {
-        sync();
-        const std::vector<float> ones(ns, 1.f);
-        HIP_LEGACY(hipMemcpy(scl.p, ones.data(), ns * sizeof(float), hipMemcpyHostToDevice));
-      }
-      std::vector<MlpJob> mj;
-      std::vector<SensJob> sj;
-      for (int g = 0; g < G_; ++g) {
-        mj.push_back(mlp_job(g, s, false, true, false));
-        sj.push_back(SensJob{models_[g].params.p, scl.p + (size_t)g * D.T});
-      }
-      upload(tj, mj);
-      upload(tsj, sj);
+      scale_or_ones(scl, scale, (size_t)G_ * D.T);
+      eval_jobs(s, tj, &tsj, scl.p);
       part.alloc(sens_part_floats(D.R, G_, md_.KS1), false);
       res.alloc(host.size(), false);
       launch_input_sens(as<MlpJob>(tj), as<SensJob>(tsj), G_, D.R, md_.md, md_.KS1, md_.s[0],
                         part.p, res.p, st_);
       sync();
-      HIP_LEGACY(hipMemcpy(host.data(), res.p, host.size() * sizeof(double), hipMemcpyDeviceToHost));
+      fetch(host.data(), res.p, host.size());
     }
     py::array_t<double> a({G_, C}), b({G_, C}), e({C});
     for (int g = 0; g < G_; ++g)
@@ -829,11 +845,10 @@ class Engine {
   // k_macro_sens + reduce).
   bool macro_sens_ok() const { return macro_sens_supported(md_.md, md_.KS1, md_.nrnn, md_.H, G_); }
   py::dict macro_sensitivity(int s, uintptr_t scale, int lags, bool refresh = true) {
-    if (s < 0 || s > 2) throw std::invalid_argument("split must be 0, 1 or 2");
+    check_split(s, "macro_sensitivity", kSplitIndex);
     if (lags < 1) throw std::invalid_argument("macro_sensitivity: lags must be >= 1");
     ensure_jobs();
-    const SplitDev& D = splits_[s];
-    if (!D.set) throw std::runtime_error("split not set");
+    const SplitDev& D = check_split(s, "macro_sensitivity", kSplitSet);
     if (md_.nrnn == 0) throw std::invalid_argument("macro_sensitivity: the model has no LSTM (the state columns are the macro series)");
     if (md_.nrnn != 1 || md_.H > 8)
       throw std::invalid_argument("macro_sensitivity: not available for stacked LSTMs or more than 8 units");
@@ -852,45 +867,32 @@ class Engine {
       DevBuf<float> scl, part, C, sg, sc, sh;
       DevBuf<double> res;
       const size_t ns = (size_t)G_ * D.T, H = md_.H;
-      scl.alloc(ns, false);
-      if (scale) {
-        HIP_OK(hipMemcpyAsync(scl.p, reinterpret_cast<const void*>(scale), ns * sizeof(float),
-                              hipMemcpyDeviceToDevice, st_));
-      } else {
-        sync();
-        const std::vector<float> ones(ns, 1.f);
-        HIP_LEGACY(hipMemcpy(scl.p, ones.data(), ns * sizeof(float), hipMemcpyHostToDevice));
-      }
+      scale_or_ones(scl, scale, ns);
       sg.alloc(ns * 4 * H); sc.alloc(ns * H); sh.alloc(ns * H);
       C.alloc(macro_c_floats(A));                    // (zero-filled: padding and t - l < 0)
-      std::vector<MlpJob> mj;
-      std::vector<SensJob> sj;
+      eval_jobs(s, tj, &tsj, scl.p);
       std::vector<RnnJob> rj;
       std::vector<LagJob> lj;
       for (int g = 0; g < G_; ++g) {
-        mj.push_back(mlp_job(g, s, false, true, false));
-        sj.push_back(SensJob{models_[g].params.p, scl.p + (size_t)g * D.T});
         RnnJob r = rnn_job(g, s, false, 0);
         r.sg = sg.p + (size_t)g * D.T * 4 * H; r.sc = sc.p + (size_t)g * D.T * H; r.sh = sh.p + (size_t)g * D.T * H;
         rj.push_back(r);
         lj.push_back(LagJob{models_[g].params.p, r.sg, r.sc, r.c0});
       }
-      upload(tj, mj); upload(tsj, sj); upload(trj, rj); upload(tlj, lj);
+      upload(trj, rj); upload(tlj, lj);
       part.alloc(macro_part_floats(A), false);
       res.alloc(host.size(), false);
-      hipEvent_t ev[4];
-      for (auto& e : ev) HIP_OK(hipEventCreate(&e));
-      HIP_OK(hipEventRecord(ev[0], st_));
+      GpuTimer tm(st_, 4);
+      tm.mark();
       launch_prologue(as<RnnJob>(trj), G_, D.T, dd(), md_, st_, false, true);
-      HIP_OK(hipEventRecord(ev[1], st_));
+      tm.mark();
       launch_lstm_lagjac(as<LagJob>(tlj), A, C.p, st_);
-      HIP_OK(hipEventRecord(ev[2], st_));
+      tm.mark();
       launch_macro_sens(as<MlpJob>(tj), as<SensJob>(tsj), A, md_.md, md_.KS1, md_.s[0], C.p, part.p, res.p, st_);
-      HIP_OK(hipEventRecord(ev[3], st_));
+      tm.mark();
       sync();
-      for (int i = 0; i < 3; ++i) HIP_OK(hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]));
-      for (auto& e : ev) HIP_OK(hipEventDestroy(e));
-      HIP_LEGACY(hipMemcpy(host.data(), res.p, host.size() * sizeof(double), hipMemcpyDeviceToHost));
+      for (int i = 0; i < 3; ++i) ms[i] = tm.ms(i);
+      fetch(host.data(), res.p, host.size());
     }
     (void)nrows;
     py::array_t<double> a({G_, L, M}), e({L, M}), c({M});
@@ -916,23 +918,18 @@ class Engine {
   // for an empty period), rows (= R) and gpu_ms.
   py::dict sorted_portfolios(int s, int quantiles, std::vector<int> cols, uintptr_t extra_keys, int n_extra,
                              uintptr_t values, int n_values) {
-    if (s < 0 || s > 2) throw std::invalid_argument("split must be 0, 1 or 2");
+    check_split(s, "sorted_portfolios", kSplitIndex);
     if (quantiles < 2 || quantiles > QSORT_MAX_Q) throw std::invalid_argument("sorted_portfolios: quantiles must be in [2, 16]");
     if (n_values < 0 || n_values > QSORT_MAX_VALUES) throw std::invalid_argument("sorted_portfolios: n_values must be in [0, 4]");
     if (n_extra < 0 || (n_extra > 0 && !extra_keys)) throw std::invalid_argument("sorted_portfolios: n_extra needs extra_keys");
     if (n_values > 0 && !values) throw std::invalid_argument("sorted_portfolios: n_values needs values");
     for (int c : cols)
       if (c < 0 || c >= md_.F) throw std::invalid_argument("sorted_portfolios: column outside [0, F)");
-    const SplitDev& D = splits_[s];
-    if (!D.set) throw std::runtime_error("split not set");
+    const SplitDev& D = check_split(s, "sorted_portfolios", kSplitSet | kSplitPeriods);
     const int Q = quantiles, K1 = 1 + n_values, C = cols.empty() ? md_.F : (int)cols.size(), P = C + n_extra;
-    if (D.T > 65535) throw std::invalid_argument("sorted_portfolios: more than 65535 periods");
-    py::array_t<int> cnt({D.T, P, Q});
-    py::array_t<double> sum({D.T, P, Q, K1});
-    py::array_t<float> brk({D.T, P, Q - 1});
-    std::fill_n(cnt.mutable_data(), cnt.size(), 0);
-    std::fill_n(sum.mutable_data(), sum.size(), 0.0);
-    std::fill_n(brk.mutable_data(), brk.size(), std::nanf(""));
+    auto cnt = filled<int>({D.T, P, Q}, 0);
+    auto sum = filled<double>({D.T, P, Q, K1}, 0.0);
+    auto brk = filled<float>({D.T, P, Q - 1}, std::nanf(""));
     float ms = 0.f;
     if (D.R > 0 && D.T > 0 && P > 0) {        // (an empty split launches nothing and reads nothing)
       DevBuf<int> dcols, dcnt;
@@ -941,23 +938,15 @@ class Engine {
       if (!cols.empty()) up(dcols, cols.data(), cols.size());
       dcnt.alloc((size_t)cnt.size(), false); dsum.alloc((size_t)sum.size(), false); dbrk.alloc((size_t)brk.size(), false);
       QsortArgs A{};
-      A.X = D.X.p; A.KP = md_.KP; A.fp32 = md_.md.fp32 ? 1 : 0;
-      A.Rc = D.Rc.p; A.rowti = reinterpret_cast<const int2*>(D.rowti.p); A.row_ptr = D.row_ptr.p;
-      A.T = D.T; A.N = D.N; A.Q = Q; A.C = C; A.cols = dcols.p; A.E = n_extra;
+      A.pv = panel_view(D);
+      A.Q = Q; A.C = C; A.cols = dcols.p; A.E = n_extra;
       A.extra = reinterpret_cast<const float*>(extra_keys);
       A.K = n_values; A.values = reinterpret_cast<const float*>(values);
       A.count = dcnt.p; A.sum = dsum.p; A.breaks = dbrk.p;
-      hipEvent_t ev[2];
-      for (auto& e : ev) HIP_OK(hipEventCreate(&e));
-      HIP_OK(hipEventRecord(ev[0], st_));
-      launch_qsort_port(A, st_);
-      HIP_OK(hipEventRecord(ev[1], st_));
-      sync();
-      HIP_OK(hipEventElapsedTime(&ms, ev[0], ev[1]));
-      for (auto& e : ev) HIP_OK(hipEventDestroy(e));
-      HIP_LEGACY(hipMemcpy(cnt.mutable_data(), dcnt.p, cnt.size() * sizeof(int), hipMemcpyDeviceToHost));
-      HIP_LEGACY(hipMemcpy(sum.mutable_data(), dsum.p, sum.size() * sizeof(double), hipMemcpyDeviceToHost));
-      if (brk.size()) HIP_LEGACY(hipMemcpy(brk.mutable_data(), dbrk.p, brk.size() * sizeof(float), hipMemcpyDeviceToHost));
+      ms = timed([&] { launch_qsort_port(A, st_); });
+      fetch(cnt, dcnt.p);
+      fetch(sum, dsum.p);
+      fetch(brk, dbrk.p);
     }
     py::dict d;
     d["count"] = cnt; d["sum"] = sum; d["breaks"] = brk; d["rows"] = D.R; d["gpu_ms"] = ms;
@@ -974,7 +963,7 @@ class Engine {
   // rows (= R) and gpu_ms. An empty pair list returns empty arrays and launches nothing.
   py::dict double_sorted_portfolios(int s, std::vector<std::pair<int, int>> pairs, int qa, int qb, bool conditional,
                                     uintptr_t extra_keys, int n_extra, uintptr_t values, int n_values) {
-    if (s < 0 || s > 2) throw std::invalid_argument("split must be 0, 1 or 2");
+    check_split(s, "double_sorted_portfolios", kSplitIndex);
     if (qa < 2 || qa > QSORT2_MAX_Q || qb < 2 || qb > QSORT2_MAX_Q)
       throw std::invalid_argument("double_sorted_portfolios: qa and qb must be in [2, 16]");
     if (qa * qb > QSORT2_MAX_CELLS) throw std::invalid_argument("double_sorted_portfolios: qa * qb must be at most 36");
@@ -984,17 +973,11 @@ class Engine {
     for (const auto& pr : pairs)
       if (pr.first < 0 || pr.first >= md_.F + n_extra || pr.second < 0 || pr.second >= md_.F + n_extra)
         throw std::invalid_argument("double_sorted_portfolios: key index outside [0, F + n_extra)");
-    const SplitDev& D = splits_[s];
-    if (!D.set) throw std::runtime_error("split not set");
-    if (D.T > 65535) throw std::invalid_argument("double_sorted_portfolios: more than 65535 periods");
+    const SplitDev& D = check_split(s, "double_sorted_portfolios", kSplitSet | kSplitPeriods);
     const int K1 = 1 + n_values, P = (int)pairs.size();
-    py::array_t<int> cnt({D.T, P, qa, qb});
-    py::array_t<double> sum({D.T, P, qa, qb, K1});
-    py::array_t<float> bra({D.T, P, qa - 1}), brb({D.T, P, qa, qb - 1});
-    std::fill_n(cnt.mutable_data(), cnt.size(), 0);
-    std::fill_n(sum.mutable_data(), sum.size(), 0.0);
-    std::fill_n(bra.mutable_data(), bra.size(), std::nanf(""));
-    std::fill_n(brb.mutable_data(), brb.size(), std::nanf(""));
+    auto cnt = filled<int>({D.T, P, qa, qb}, 0);
+    auto sum = filled<double>({D.T, P, qa, qb, K1}, 0.0);
+    auto bra = filled<float>({D.T, P, qa - 1}, std::nanf("")), brb = filled<float>({D.T, P, qa, qb - 1}, std::nanf(""));
     float ms = 0.f;
     if (D.R > 0 && D.T > 0 && P > 0) {        // (an empty split or pair list launches nothing)
       std::vector<int> flat;
@@ -1006,25 +989,17 @@ class Engine {
       dcnt.alloc((size_t)cnt.size(), false); dsum.alloc((size_t)sum.size(), false);
       dbra.alloc((size_t)bra.size(), false); dbrb.alloc((size_t)brb.size(), false);
       Qsort2Args A{};
-      A.X = D.X.p; A.KP = md_.KP; A.fp32 = md_.md.fp32 ? 1 : 0;
-      A.Rc = D.Rc.p; A.rowti = reinterpret_cast<const int2*>(D.rowti.p); A.row_ptr = D.row_ptr.p;
-      A.T = D.T; A.N = D.N; A.F = md_.F; A.P = P; A.pairs = reinterpret_cast<const int2*>(dpairs.p);
+      A.pv = panel_view(D);
+      A.P = P; A.pairs = reinterpret_cast<const int2*>(dpairs.p);
       A.Qa = qa; A.Qb = qb; A.conditional = conditional ? 1 : 0;
       A.E = n_extra; A.extra = reinterpret_cast<const float*>(extra_keys);
       A.K = n_values; A.values = reinterpret_cast<const float*>(values);
       A.count = dcnt.p; A.sum = dsum.p; A.breaks_a = dbra.p; A.breaks_b = dbrb.p;
-      hipEvent_t ev[2];
-      for (auto& e : ev) HIP_OK(hipEventCreate(&e));
-      HIP_OK(hipEventRecord(ev[0], st_));
-      launch_qsort2_port(A, st_);
-      HIP_OK(hipEventRecord(ev[1], st_));
-      sync();
-      HIP_OK(hipEventElapsedTime(&ms, ev[0], ev[1]));
-      for (auto& e : ev) HIP_OK(hipEventDestroy(e));
-      HIP_LEGACY(hipMemcpy(cnt.mutable_data(), dcnt.p, cnt.size() * sizeof(int), hipMemcpyDeviceToHost));
-      HIP_LEGACY(hipMemcpy(sum.mutable_data(), dsum.p, sum.size() * sizeof(double), hipMemcpyDeviceToHost));
-      HIP_LEGACY(hipMemcpy(bra.mutable_data(), dbra.p, bra.size() * sizeof(float), hipMemcpyDeviceToHost));
-      HIP_LEGACY(hipMemcpy(brb.mutable_data(), dbrb.p, brb.size() * sizeof(float), hipMemcpyDeviceToHost));
+      ms = timed([&] { launch_qsort2_port(A, st_); });
+      fetch(cnt, dcnt.p);
+      fetch(sum, dsum.p);
+      fetch(bra, dbra.p);
+      fetch(brb, dbrb.p);
     }
     py::dict d;
     d["count"] = cnt; d["sum"] = sum; d["breaks_a"] = bra; d["breaks_b"] = brb; d["rows"] = D.R; d["gpu_ms"] = ms;
@@ -1032,62 +1007,41 @@ class Engine {
   }
   // Linear benchmark SDFs of split s (k_linport.hip, definitions in linport.h and
   // analysis/benchmarks.py). Both methods read the panel only -- no model, job table or graph -- and
-  // cut every period into segments of LINPORT_SEG rows; fp64 sums in a fixed order, so repeated
+  // cut every period into segments of a fixed number of rows; fp64 sums in a fixed order, so repeated
   // calls are bitwise identical. An empty split returns zeros and launches nothing.
   //
-  // The segment table of the split: (period, first row within it) per segment and the periods'
-  // segment ranges, from the host copy of row_ptr. Returns the number of segments.
+  // The segment table of the split (linport_segments, from the host copy of row_ptr) on the
+  // device. Returns the number of segments.
   int lin_segments(const SplitDev& D, DevBuf<int>& dseg, DevBuf<int>& dsegptr) {
-    std::vector<int> rp((size_t)D.T + 1), seg, sp((size_t)D.T + 1, 0);
-    HIP_LEGACY(hipMemcpy(rp.data(), D.row_ptr.p, rp.size() * sizeof(int), hipMemcpyDeviceToHost));
-    for (int t = 0; t < D.T; ++t) {
-      for (int off = 0; off < rp[t + 1] - rp[t]; off += LINPORT_SEG) { seg.push_back(t); seg.push_back(off); }
-      sp[t + 1] = (int)(seg.size() / 2);
-    }
+    std::vector<int> rp((size_t)D.T + 1), seg, sp;
+    fetch(rp.data(), D.row_ptr.p, rp.size());
+    const int nseg = linport_segments(rp.data(), D.T, seg, sp);
     up(dseg, seg.data(), seg.size());
     up(dsegptr, sp.data(), sp.size());
-    return (int)(seg.size() / 2);
-  }
-  void lin_panel_args(const SplitDev& D, LinportArgs& A) {
-    A.X = D.X.p; A.KP = md_.KP; A.fp32 = md_.md.fp32 ? 1 : 0; A.F = md_.F;
-    A.Rc = D.Rc.p; A.rowti = reinterpret_cast<const int2*>(D.rowti.p); A.row_ptr = D.row_ptr.p;
-    A.T = D.T; A.N = D.N;
+    return nseg;
   }
   bool linear_supported() const { return linport_supported(md_.F); }
   // managed_portfolios: sum_x, sum_xr fp64 [T][F] (sum_i x and sum_i x R over the valid rows of each
   // period, x as the engine stores it), n int32 [T], rows (= R) and gpu_ms.
   py::dict managed_portfolios(int s) {
-    if (s < 0 || s > 2) throw std::invalid_argument("split must be 0, 1 or 2");
-    const SplitDev& D = splits_[s];
-    if (!D.set) throw std::runtime_error("split not set");
-    if (D.T > 65535) throw std::invalid_argument("managed_portfolios: more than 65535 periods");
+    const SplitDev& D = check_split(s, "managed_portfolios", kSplitIndex | kSplitSet | kSplitPeriods);
     const int F = md_.F;
-    py::array_t<double> sx({D.T, F}), sxr({D.T, F});
-    py::array_t<int> nn(D.T);
-    std::fill_n(sx.mutable_data(), sx.size(), 0.0);
-    std::fill_n(sxr.mutable_data(), sxr.size(), 0.0);
-    std::fill_n(nn.mutable_data(), nn.size(), 0);
+    auto sx = filled<double>({D.T, F}, 0.0), sxr = filled<double>({D.T, F}, 0.0);
+    auto nn = filled<int>({D.T}, 0);
     float ms = 0.f;
     if (D.R > 0 && D.T > 0) {
       DevBuf<int> dseg, dsp, dn;
       DevBuf<double> part, out;
       LinportArgs A{};
-      lin_panel_args(D, A);
+      A.pv = panel_view(D);
       A.nseg = lin_segments(D, dseg, dsp);
       A.seg = reinterpret_cast<const int2*>(dseg.p); A.seg_ptr = dsp.p;
       part.alloc((size_t)A.nseg * 2 * F, false); out.alloc((size_t)2 * D.T * F, false); dn.alloc(D.T, false);
       A.part = part.p; A.out = out.p; A.n = dn.p;
-      hipEvent_t ev[2];
-      for (auto& e : ev) HIP_OK(hipEventCreate(&e));
-      HIP_OK(hipEventRecord(ev[0], st_));
-      launch_managed(A, st_);
-      HIP_OK(hipEventRecord(ev[1], st_));
-      sync();
-      HIP_OK(hipEventElapsedTime(&ms, ev[0], ev[1]));
-      for (auto& e : ev) HIP_OK(hipEventDestroy(e));
-      HIP_LEGACY(hipMemcpy(sx.mutable_data(), out.p, sx.size() * sizeof(double), hipMemcpyDeviceToHost));
-      HIP_LEGACY(hipMemcpy(sxr.mutable_data(), out.p + sx.size(), sxr.size() * sizeof(double), hipMemcpyDeviceToHost));
-      HIP_LEGACY(hipMemcpy(nn.mutable_data(), dn.p, nn.size() * sizeof(int), hipMemcpyDeviceToHost));
+      ms = timed([&] { launch_managed(A, st_); });
+      fetch(sx, out.p);
+      fetch(sxr, out.p + sx.size());
+      fetch(nn, dn.p);
     }
     py::dict d;
     d["sum_x"] = sx; d["sum_xr"] = sxr; d["n"] = nn; d["rows"] = D.R; d["gpu_ms"] = ms;
@@ -1099,15 +1053,13 @@ class Engine {
   // s2, sr fp64 [T][K], n int32 [T], sum_r, sum_rr fp64 [T], rows and gpu_ms.
   py::dict linear_portfolios(int s, py::array_t<float, py::array::c_style | py::array::forcecast> theta,
                              py::object center, uintptr_t w_out) {
-    if (s < 0 || s > 2) throw std::invalid_argument("split must be 0, 1 or 2");
+    check_split(s, "linear_portfolios", kSplitIndex);
     if (theta.ndim() != 2 || theta.shape(1) != md_.F) throw std::invalid_argument("linear_portfolios: theta must be [K][F]");
     const int K = (int)theta.shape(0), F = md_.F;
     if (K < 1 || K > LINPORT_MAX_K) throw std::invalid_argument("linear_portfolios: K must be in [1, 64]");
     if (!linport_supported(F))
       throw std::invalid_argument("linear_portfolios: not available for this shape (theta exceeds the LDS budget)");
-    const SplitDev& D = splits_[s];
-    if (!D.set) throw std::runtime_error("split not set");
-    if (D.T > 65535) throw std::invalid_argument("linear_portfolios: more than 65535 periods");
+    const SplitDev& D = check_split(s, "linear_portfolios", kSplitSet | kSplitPeriods);
     py::array_t<float, py::array::c_style | py::array::forcecast> cen;
     const bool has_c = !center.is_none();
     if (has_c) {
@@ -1115,10 +1067,9 @@ class Engine {
       if (!cen || cen.ndim() != 2 || cen.shape(0) != D.T || cen.shape(1) != K)
         throw std::invalid_argument("linear_portfolios: center must be [T][K]");
     }
-    py::array_t<double> r1({D.T, K}), ra({D.T, K}), r2({D.T, K}), rr({D.T, K}), sr(D.T), srr(D.T);
-    py::array_t<int> nn(D.T);
-    for (auto* a : {&r1, &ra, &r2, &rr, &sr, &srr}) std::fill_n(a->mutable_data(), a->size(), 0.0);
-    std::fill_n(nn.mutable_data(), nn.size(), 0);
+    auto r1 = filled<double>({D.T, K}, 0.0), ra = filled<double>({D.T, K}, 0.0), r2 = filled<double>({D.T, K}, 0.0),
+         rr = filled<double>({D.T, K}, 0.0), sr = filled<double>({D.T}, 0.0), srr = filled<double>({D.T}, 0.0);
+    auto nn = filled<int>({D.T}, 0);
     float ms = 0.f;
     if (D.R > 0 && D.T > 0) {
       DevBuf<int> dseg, dsp, dn;
@@ -1129,7 +1080,7 @@ class Engine {
       up(dth, packed.data(), packed.size());
       if (has_c) up(dc, cen.data(), (size_t)cen.size());
       LinportArgs A{};
-      lin_panel_args(D, A);
+      A.pv = panel_view(D);
       A.nseg = lin_segments(D, dseg, dsp);
       A.seg = reinterpret_cast<const int2*>(dseg.p); A.seg_ptr = dsp.p;
       A.K = K; A.theta = dth.p; A.center = has_c ? dc.p : nullptr; A.w_out = reinterpret_cast<float*>(w_out);
@@ -1137,20 +1088,12 @@ class Engine {
       part.alloc(linport_part_doubles(A.nseg, K), false); partr.alloc((size_t)A.nseg * 2, false);
       out.alloc(4 * TK, false); outr.alloc((size_t)2 * D.T, false); dn.alloc(D.T, false);
       A.part = part.p; A.part_r = partr.p; A.out = out.p; A.out_r = outr.p; A.n = dn.p;
-      hipEvent_t ev[2];
-      for (auto& e : ev) HIP_OK(hipEventCreate(&e));
-      HIP_OK(hipEventRecord(ev[0], st_));
-      launch_linport(A, st_);
-      HIP_OK(hipEventRecord(ev[1], st_));
-      sync();
-      HIP_OK(hipEventElapsedTime(&ms, ev[0], ev[1]));
-      for (auto& e : ev) HIP_OK(hipEventDestroy(e));
+      ms = timed([&] { launch_linport(A, st_); });
       int j = 0;
-      for (auto* a : {&r1, &ra, &r2, &rr})
-        HIP_LEGACY(hipMemcpy(a->mutable_data(), out.p + TK * j++, TK * sizeof(double), hipMemcpyDeviceToHost));
-      HIP_LEGACY(hipMemcpy(sr.mutable_data(), outr.p, D.T * sizeof(double), hipMemcpyDeviceToHost));
-      HIP_LEGACY(hipMemcpy(srr.mutable_data(), outr.p + D.T, D.T * sizeof(double), hipMemcpyDeviceToHost));
-      HIP_LEGACY(hipMemcpy(nn.mutable_data(), dn.p, nn.size() * sizeof(int), hipMemcpyDeviceToHost));
+      for (auto* a : {&r1, &ra, &r2, &rr}) fetch(*a, out.p + TK * j++);
+      fetch(sr, outr.p);
+      fetch(srr, outr.p + D.T);
+      fetch(nn, dn.p);
     }
     py::dict d;
     d["s1"] = r1; d["sa"] = ra; d["s2"] = r2; d["sr"] = rr; d["n"] = nn; d["sum_r"] = sr; d["sum_rr"] = srr;
@@ -1164,15 +1107,10 @@ class Engine {
   // identical. An empty split returns zeros and launches nothing.
   int xgram_run() const { return ::xgram_run(); }
   py::dict characteristic_gram(int s) {
-    if (s < 0 || s > 2) throw std::invalid_argument("split must be 0, 1 or 2");
-    const SplitDev& D = splits_[s];
-    if (!D.set) throw std::runtime_error("split not set");
-    if (D.T > 65535) throw std::invalid_argument("characteristic_gram: more than 65535 periods");
+    const SplitDev& D = check_split(s, "characteristic_gram", kSplitIndex | kSplitSet | kSplitPeriods);
     const int F = md_.F;
-    py::array_t<double> g({(py::ssize_t)D.T, (py::ssize_t)F, (py::ssize_t)F}), sr(D.T), srr(D.T);
-    py::array_t<int> nn(D.T);
-    for (auto* a : {&g, &sr, &srr}) std::fill_n(a->mutable_data(), a->size(), 0.0);
-    std::fill_n(nn.mutable_data(), nn.size(), 0);
+    auto g = filled<double>({D.T, F, F}, 0.0), sr = filled<double>({D.T}, 0.0), srr = filled<double>({D.T}, 0.0);
+    auto nn = filled<int>({D.T}, 0);
     float ms = 0.f;
     if (D.R > 0 && D.T > 0) {
       DevBuf<int> dtiles, dn;
@@ -1181,23 +1119,15 @@ class Engine {
       xgram_tiles(F, tiles);
       up(dtiles, tiles.data(), tiles.size());
       XgramArgs A{};
-      A.X = D.X.p; A.KP = md_.KP; A.fp32 = md_.md.fp32 ? 1 : 0; A.F = F;
-      A.Rc = D.Rc.p; A.row_ptr = D.row_ptr.p; A.T = D.T;
+      A.pv = panel_view(D);
       A.tiles = reinterpret_cast<const int2*>(dtiles.p); A.ntiles = (int)(tiles.size() / 2);
       dg.alloc((size_t)g.size(), false); dr.alloc((size_t)2 * D.T, false); dn.alloc(D.T, false);
       A.gram = dg.p; A.sum_r = dr.p; A.n = dn.p;
-      hipEvent_t ev[2];
-      for (auto& e : ev) HIP_OK(hipEventCreate(&e));
-      HIP_OK(hipEventRecord(ev[0], st_));
-      launch_xgram(A, st_);
-      HIP_OK(hipEventRecord(ev[1], st_));
-      sync();
-      HIP_OK(hipEventElapsedTime(&ms, ev[0], ev[1]));
-      for (auto& e : ev) HIP_OK(hipEventDestroy(e));
-      HIP_LEGACY(hipMemcpy(g.mutable_data(), dg.p, (size_t)g.size() * sizeof(double), hipMemcpyDeviceToHost));
-      HIP_LEGACY(hipMemcpy(sr.mutable_data(), dr.p, D.T * sizeof(double), hipMemcpyDeviceToHost));
-      HIP_LEGACY(hipMemcpy(srr.mutable_data(), dr.p + D.T, D.T * sizeof(double), hipMemcpyDeviceToHost));
-      HIP_LEGACY(hipMemcpy(nn.mutable_data(), dn.p, nn.size() * sizeof(int), hipMemcpyDeviceToHost));
+      ms = timed([&] { launch_xgram(A, st_); });
+      fetch(g, dg.p);
+      fetch(sr, dr.p);
+      fetch(srr, dr.p + D.T);
+      fetch(nn, dn.p);
     }
     py::dict d;
     d["gram"] = g; d["n"] = nn; d["sum_r"] = sr; d["sum_rr"] = srr; d["rows"] = D.R; d["gpu_ms"] = ms;
@@ -1216,11 +1146,10 @@ class Engine {
   // split returns zeros and launches nothing.
   py::dict pred_loss(int s, py::object factor, const std::string& weighting, bool refresh = true,
                      bool write_dw = false) {
-    if (s < 0 || s > 2) throw std::invalid_argument("split must be 0, 1 or 2");
+    check_split(s, "pred_loss", kSplitIndex);
     if (write_dw && s != 0) throw std::invalid_argument("pred_loss: dw exists for the train split only");
     ensure_jobs();
-    const SplitDev& D = splits_[s];
-    if (!D.set) throw std::runtime_error("split not set");
+    const SplitDev& D = check_split(s, "pred_loss", kSplitSet);
     const int wt = pred_weighting(weighting);
     sync();
     fit_ready_ = false;                       // (the split's tables are rebuilt: a fit begins again)
@@ -1241,9 +1170,8 @@ class Engine {
       sync();
       const size_t per = (size_t)PRED_NSUM * D.T;
       for (int g = 0; g < G_; ++g) {
-        HIP_LEGACY(hipMemcpy(sums.mutable_data() + (size_t)g * per, fitm_[g].sums[s].p, per * sizeof(double),
-                             hipMemcpyDeviceToHost));
-        HIP_LEGACY(hipMemcpy(loss.mutable_data() + g, fitm_[g].loss.p + s, sizeof(double), hipMemcpyDeviceToHost));
+        fetch(sums.mutable_data() + (size_t)g * per, fitm_[g].sums[s].p, per);
+        fetch(loss.mutable_data() + g, fitm_[g].loss.p + s, 1);
       }
     }
     py::dict d;
@@ -1357,7 +1285,7 @@ class Engine {
   }
   py::dict weight_surface(int s, uintptr_t scale, std::vector<float> grid, std::vector<float> base,
                           std::vector<std::pair<int, int>> items, bool refresh = true) {
-    if (s < 0 || s > 2) throw std::invalid_argument("weight_surface: split must be 0, 1 or 2");
+    check_split(s, "weight_surface", kSplitIndex, true);
     const int P = (int)grid.size(), F = md_.F;
     if (grid.size() < 2 || grid.size() > WSURF_MAX_P) throw std::invalid_argument("weight_surface: the grid must have 2 .. 64 points");
     if ((int)base.size() != F) throw std::invalid_argument("weight_surface: base must have F entries");
@@ -1372,7 +1300,7 @@ class Engine {
     }
     const long long rows = (long long)n1 * P + (long long)n2 * P * P;
     if (rows > (1ll << 30)) throw std::invalid_argument("weight_surface: more than 2^30 rows");
-    if (!splits_[s].set) throw std::invalid_argument("weight_surface: split not set");
+    check_split(s, "weight_surface", kSplitSet, true);
     ensure_jobs();
     const SplitDev& D = splits_[s];
     if (!wsurf_supported(md_.md, md_.KS1, D.T))
@@ -1385,17 +1313,7 @@ class Engine {
     DevBuf<char> tj;
     DevBuf<float> scl, dgrid, dbase, res;
     DevBuf<int2> ditems;
-    const size_t ns = (size_t)G_ * D.T;
-    scl.alloc(ns, false);
-    if (scale) {
-      HIP_OK(hipMemcpyAsync(scl.p, reinterpret_cast<const void*>(scale), ns * sizeof(float),
-                            hipMemcpyDeviceToDevice, st_));
-    }
-    sync();
-    if (!scale) {
-      const std::vector<float> ones(ns, 1.f);
-      HIP_LEGACY(hipMemcpy(scl.p, ones.data(), ns * sizeof(float), hipMemcpyHostToDevice));
-    }
+    scale_or_ones(scl, scale, (size_t)G_ * D.T);
     std::vector<float> hb((size_t)md_.KP, 0.f);
     std::copy(base.begin(), base.end(), hb.begin());
     std::vector<int2> hi;
@@ -1403,24 +1321,15 @@ class Engine {
     up(dgrid, grid.data(), grid.size());
     up(dbase, hb.data(), hb.size());
     up(ditems, hi.data(), hi.size());
-    std::vector<MlpJob> mj;
-    for (int g = 0; g < G_; ++g) mj.push_back(mlp_job(g, s, false, true, false));
-    upload(tj, mj);
+    eval_jobs(s, tj);
     res.alloc((size_t)rows, false);
     WsurfArgs A{};
     A.scale = scl.p; A.grid = dgrid.p; A.base = dbase.p; A.items = ditems.p;
     A.n1 = n1; A.n2 = n2; A.P = P; A.rows = (int)rows; A.G = G_; A.T = D.T; A.out = res.p;
-    float ms = 0.f;
-    hipEvent_t ev[2];
-    for (auto& e : ev) HIP_OK(hipEventCreate(&e));
-    HIP_OK(hipEventRecord(ev[0], st_));
-    const WsurfPlan plan = launch_weight_surface(as<MlpJob>(tj), A, md_.md, md_.KS1, st_);
-    HIP_OK(hipEventRecord(ev[1], st_));
-    sync();
-    HIP_OK(hipEventElapsedTime(&ms, ev[0], ev[1]));
-    for (auto& e : ev) HIP_OK(hipEventDestroy(e));
+    WsurfPlan plan{};
+    const float ms = timed([&] { plan = launch_weight_surface(as<MlpJob>(tj), A, md_.md, md_.KS1, st_); });
     py::array_t<float> vals((py::ssize_t)rows);
-    HIP_LEGACY(hipMemcpy(vals.mutable_data(), res.p, (size_t)rows * sizeof(float), hipMemcpyDeviceToHost));
+    fetch(vals, res.p);
     py::dict d;
     d["values"] = vals; d["rows"] = (long long)rows; d["gpu_ms"] = ms; d["tiles_per_wave"] = plan.tiles_per_wave;
     d["period_split"] = plan.period_split;
@@ -2028,6 +1937,75 @@ class Engine {
     if (!v.empty()) HIP_LEGACY(hipMemcpy(b.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
     return b;
   }
+
+  // ---- host plumbing of the analysis passes ------------------------------------------------
+  // The split checks of an analysis pass, each made where `what` asks for it (the passes keep the
+  // order of their argument checks): the index, that the split's data is set, and the 65535
+  // periods the panel launchers accept. `who` names the method in the period message;
+  // own_prefix (weight_surface): every message carries it and all are std::invalid_argument.
+  enum : unsigned { kSplitIndex = 1, kSplitSet = 2, kSplitPeriods = 4 };
+  const SplitDev& check_split(int s, const char* who, unsigned what, bool own_prefix = false) const {
+    const std::string pre = own_prefix ? std::string(who) + ": " : std::string();
+    if ((what & kSplitIndex) && (s < 0 || s > 2)) throw std::invalid_argument(pre + "split must be 0, 1 or 2");
+    const SplitDev& D = splits_[s];
+    if ((what & kSplitSet) && !D.set) {
+      if (own_prefix) throw std::invalid_argument(pre + "split not set");
+      throw std::runtime_error("split not set");
+    }
+    if ((what & kSplitPeriods) && D.T > 65535)
+      throw std::invalid_argument(std::string(who) + ": more than 65535 periods");
+    return D;
+  }
+  // The one place that fills the panel-only kernels' view of a split (panel_view.h)
+  PanelView panel_view(const SplitDev& D) const {
+    PanelView v{};
+    v.X = D.X.p; v.KP = md_.KP; v.fp32 = md_.md.fp32 ? 1 : 0; v.F = md_.F;
+    v.Rc = D.Rc.p; v.rowti = reinterpret_cast<const int2*>(D.rowti.p); v.row_ptr = D.row_ptr.p;
+    v.T = D.T; v.N = D.N;
+    return v;
+  }
+  // [G][T] factors of a model-reading pass in a buffer of the call: the caller's device array,
+  // copied on the engine stream (so ahead of the launches that follow on it), or ones
+  void scale_or_ones(DevBuf<float>& scl, uintptr_t scale, size_t ns) {
+    scl.alloc(ns, false);
+    if (scale) {
+      HIP_OK(hipMemcpyAsync(scl.p, reinterpret_cast<const void*>(scale), ns * sizeof(float),
+                            hipMemcpyDeviceToDevice, st_));
+    } else {
+      sync();
+      const std::vector<float> ones(ns, 1.f);
+      HIP_LEGACY(hipMemcpy(scl.p, ones.data(), ns * sizeof(float), hipMemcpyHostToDevice));
+    }
+  }
+  // Evaluation-mode tower jobs of split s, one per model; with sens also the SensJob table
+  // (model g's parameters and row g of the [G][T] factors scl)
+  void eval_jobs(int s, DevBuf<char>& jobs, DevBuf<char>* sens = nullptr, const float* scl = nullptr) {
+    std::vector<MlpJob> mj;
+    std::vector<SensJob> sj;
+    for (int g = 0; g < G_; ++g) {
+      mj.push_back(mlp_job(g, s, false, true, false));
+      if (sens) sj.push_back(SensJob{models_[g].params.p, scl + (size_t)g * splits_[s].T});
+    }
+    upload(jobs, mj);
+    if (sens) upload(*sens, sj);
+  }
+  // GPU time of what `launch` puts on the engine stream; returns with the stream synchronised
+  template <class F>
+  float timed(F&& launch) {
+    GpuTimer tm(st_);
+    tm.mark();
+    launch();
+    tm.mark();
+    sync();
+    return tm.ms();
+  }
+  // n results of a finished pass (the caller has synchronised) from the device: one blocking copy
+  template <typename T>
+  void fetch(T* dst, const T* src, size_t n) {
+    if (n) HIP_LEGACY(hipMemcpy(dst, src, n * sizeof(T), hipMemcpyDeviceToHost));
+  }
+  template <typename T>
+  void fetch(py::array_t<T>& dst, const T* src) { fetch(dst.mutable_data(), src, (size_t)dst.size()); }
 
   void pack(int g, bool wait = true) {
     launch_pack(nullptr, as<UpdJob>(j_pack_) + g, 1, reinterpret_cast<const ModelDesc*>(d_desc_.p), md_, st_);
@@ -3156,8 +3134,7 @@ class Engine {
   // fp32(1 / R) pooled.
   void pred_prepare(int s, const py::object& factor, int weighting) {
     FitSplit& S = fit_[s];
-    const SplitDev& D = splits_[s];
-    if (D.T > 65535) throw std::invalid_argument("prediction towers: more than 65535 periods");
+    const SplitDev& D = check_split(s, "prediction towers", kSplitPeriods);
     std::vector<int> rp((size_t)D.T + 1, 0);
     if (D.T > 0) HIP_LEGACY(hipMemcpy(rp.data(), D.row_ptr.p, rp.size() * sizeof(int), hipMemcpyDeviceToHost));
     S.n.assign(D.T, 0);

@@ -51,11 +51,11 @@ DLAP_DEV float x_at(const void* X, size_t idx) {
 template <bool F32>
 __global__ __launch_bounds__(kNT) void k_managed(LinportArgs a) {
   const int2 sg = gp(a.seg)[blockIdx.x];
-  const int r0 = gp(a.row_ptr)[sg.x] + sg.y;
-  const int cnt = min(LINPORT_SEG, gp(a.row_ptr)[sg.x + 1] - r0);
+  const int r0 = gp(a.pv.row_ptr)[sg.x] + sg.y;
+  const int cnt = min(LINPORT_SEG, gp(a.pv.row_ptr)[sg.x + 1] - r0);
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int f = blockIdx.y * 64 + lane;
-  const bool live = f < a.F;
+  const bool live = f < a.pv.F;
   const int col = live ? f : 0;
   double sx = 0.0, sxr = 0.0;
   for (int j0 = w; j0 < cnt; j0 += kWaves * kMU) {
@@ -64,8 +64,8 @@ __global__ __launch_bounds__(kNT) void k_managed(LinportArgs a) {
     for (int k = 0; k < kMU; ++k) {
       const int j = j0 + k * kWaves;
       const int row = r0 + (j < cnt ? j : 0);        // (clamped: a dead slot re-reads the first row)
-      x[k] = x_at<F32>(a.X, (size_t)row * a.KP + col);
-      r[k] = gp(a.Rc)[row];
+      x[k] = x_at<F32>(a.pv.X, (size_t)row * a.pv.KP + col);
+      r[k] = gp(a.pv.Rc)[row];
     }
 #pragma unroll
     for (int k = 0; k < kMU; ++k) {
@@ -83,23 +83,23 @@ __global__ __launch_bounds__(kNT) void k_managed(LinportArgs a) {
     double s = red[0][h][lane];
 #pragma unroll
     for (int k = 1; k < kWaves; ++k) s += red[k][h][lane];
-    if (live) gp(a.part)[((size_t)blockIdx.x * 2 + h) * a.F + f] = s;
+    if (live) gp(a.part)[((size_t)blockIdx.x * 2 + h) * a.pv.F + f] = s;
   }
 }
 
 __global__ __launch_bounds__(kNT) void k_managed_reduce(LinportArgs a) {
   const int i = blockIdx.x * kNT + threadIdx.x;
-  if (i >= a.T * a.F) return;
-  const int t = i / a.F, f = i - t * a.F;
+  if (i >= a.pv.T * a.pv.F) return;
+  const int t = i / a.pv.F, f = i - t * a.pv.F;
   const int s0 = gp(a.seg_ptr)[t], s1 = gp(a.seg_ptr)[t + 1];
   double sx = 0.0, sxr = 0.0;
   for (int s = s0; s < s1; ++s) {
-    sx += gp(a.part)[((size_t)s * 2) * a.F + f];
-    sxr += gp(a.part)[((size_t)s * 2 + 1) * a.F + f];
+    sx += gp(a.part)[((size_t)s * 2) * a.pv.F + f];
+    sxr += gp(a.part)[((size_t)s * 2 + 1) * a.pv.F + f];
   }
   gp(a.out)[i] = sx;
-  gp(a.out)[(size_t)a.T * a.F + i] = sxr;
-  if (f == 0) gp(a.n)[t] = gp(a.row_ptr)[t + 1] - gp(a.row_ptr)[t];
+  gp(a.out)[(size_t)a.pv.T * a.pv.F + i] = sxr;
+  if (f == 0) gp(a.n)[t] = gp(a.pv.row_ptr)[t + 1] - gp(a.pv.row_ptr)[t];
 }
 
 // columns 16 c + 4 q .. + 3 of a stored row, the ones >= F replaced by 0
@@ -133,7 +133,7 @@ DLAP_DEV void lds_theta(const float* p, float (&b)[NV]) {
 template <bool F32, int NV>
 __global__ __launch_bounds__(kNT) void k_linport(LinportArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int NC = lp_chunks(a.F), nth = 4 * NC * 64 * NV;
+  const int NC = lp_chunks(a.pv.F), nth = 4 * NC * 64 * NV;
   float* th = reinterpret_cast<float*>(smem);                                  // [4 NC][64][NV]
   double* red = reinterpret_cast<double*>(smem + (size_t)nth * sizeof(float)); // [waves][4 NV 16 + 2]
   constexpr int PW = 4 * NV * 16;
@@ -142,8 +142,8 @@ __global__ __launch_bounds__(kNT) void k_linport(LinportArgs a) {
     *reinterpret_cast<f32x4*>(th + i) = ld4(gp(a.theta) + i);
   const int2 sg = gp(a.seg)[blockIdx.x];
   const int t = sg.x, K = a.K;
-  const int r0 = gp(a.row_ptr)[t] + sg.y;
-  const int cnt = min(LINPORT_SEG, gp(a.row_ptr)[t + 1] - r0);
+  const int r0 = gp(a.pv.row_ptr)[t] + sg.y;
+  const int cnt = min(LINPORT_SEG, gp(a.pv.row_ptr)[t + 1] - r0);
   const int ntiles = (cnt + 15) >> 4;
   float c[NV];
 #pragma unroll
@@ -154,7 +154,7 @@ __global__ __launch_bounds__(kNT) void k_linport(LinportArgs a) {
   __syncthreads();
 
   for (int tile = w; tile < ntiles; tile += kWaves) {
-    const size_t rowoff = (size_t)(r0 + min(tile * 16 + n, cnt - 1)) * a.KP;   // A operand: row n of the tile
+    const size_t rowoff = (size_t)(r0 + min(tile * 16 + n, cnt - 1)) * a.pv.KP;   // A operand: row n of the tile
     bool ok[4];
     int rowc[4];
     float R[4];
@@ -163,15 +163,15 @@ __global__ __launch_bounds__(kNT) void k_linport(LinportArgs a) {
       const int j = tile * 16 + 4 * q + r;
       ok[r] = j < cnt;
       rowc[r] = r0 + min(j, cnt - 1);
-      R[r] = gp(a.Rc)[rowc[r]];
+      R[r] = gp(a.pv.Rc)[rowc[r]];
     }
     f32x4 acc[NV];
 #pragma unroll
     for (int v = 0; v < NV; ++v) acc[v] = zero4();
-    f32x4 x = load_chunk<F32>(a.X, rowoff, 4 * q, a.F);
+    f32x4 x = load_chunk<F32>(a.pv.X, rowoff, 4 * q, a.pv.F);
     for (int ch = 0; ch < NC; ++ch) {
       const f32x4 cur = x;
-      if (ch + 1 < NC) x = load_chunk<F32>(a.X, rowoff, 16 * (ch + 1) + 4 * q, a.F);
+      if (ch + 1 < NC) x = load_chunk<F32>(a.pv.X, rowoff, 16 * (ch + 1) + 4 * q, a.pv.F);
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         float b[NV];
@@ -199,10 +199,10 @@ __global__ __launch_bounds__(kNT) void k_linport(LinportArgs a) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         if (!ok[r]) continue;
-        const int i = gp(a.rowti)[rowc[r]].y;
+        const int i = gp(a.pv.rowti)[rowc[r]].y;
 #pragma unroll
         for (int v = 0; v < NV; ++v)
-          if (16 * v + n < K) gp(a.w_out)[((size_t)(16 * v + n) * a.T + t) * a.N + i] = acc[v][r] - c[v];
+          if (16 * v + n < K) gp(a.w_out)[((size_t)(16 * v + n) * a.pv.T + t) * a.pv.N + i] = acc[v][r] - c[v];
       }
     }
   }
@@ -236,7 +236,7 @@ template <int NV>
 __global__ __launch_bounds__(kNT) void k_linport_reduce(LinportArgs a) {
   constexpr int PW = 4 * NV * 16;
   const int i = blockIdx.x * kNT + threadIdx.x;
-  if (i >= a.T * a.K) return;
+  if (i >= a.pv.T * a.K) return;
   const int t = i / a.K, k = i - t * a.K;
   const int s0 = gp(a.seg_ptr)[t], s1 = gp(a.seg_ptr)[t + 1];
   double x[4] = {0.0, 0.0, 0.0, 0.0}, pr = 0.0, prr = 0.0;
@@ -246,18 +246,18 @@ __global__ __launch_bounds__(kNT) void k_linport_reduce(LinportArgs a) {
     if (k == 0) { pr += gp(a.part_r)[(size_t)s * 2]; prr += gp(a.part_r)[(size_t)s * 2 + 1]; }
   }
 #pragma unroll
-  for (int j = 0; j < 4; ++j) gp(a.out)[((size_t)j * a.T + t) * a.K + k] = x[j];
+  for (int j = 0; j < 4; ++j) gp(a.out)[((size_t)j * a.pv.T + t) * a.K + k] = x[j];
   if (k == 0) {
     gp(a.out_r)[t] = pr;
-    gp(a.out_r)[a.T + t] = prr;
-    gp(a.n)[t] = gp(a.row_ptr)[t + 1] - gp(a.row_ptr)[t];
+    gp(a.out_r)[a.pv.T + t] = prr;
+    gp(a.n)[t] = gp(a.pv.row_ptr)[t + 1] - gp(a.pv.row_ptr)[t];
   }
 }
 
 template <bool F32>
 void linport_launch_nv(const LinportArgs& a, int NV, hipStream_t st) {
-  const dim3 grid((unsigned)a.nseg), block(kNT), rgrid((unsigned)((a.T * a.K + kNT - 1) / kNT));
-  const size_t sh = lp_lds_bytes(a.F, NV);
+  const dim3 grid((unsigned)a.nseg), block(kNT), rgrid((unsigned)((a.pv.T * a.K + kNT - 1) / kNT));
+  const size_t sh = lp_lds_bytes(a.pv.F, NV);
   if (NV == 1) {
     hipLaunchKernelGGL((k_linport<F32, 1>), grid, block, sh, st, a);
     hipLaunchKernelGGL((k_linport_reduce<1>), rgrid, block, 0, st, a);
@@ -278,6 +278,16 @@ size_t linport_theta_floats(int F, int K) { return (size_t)4 * lp_chunks(F) * 64
 bool linport_supported(int F) { return F >= 1 && lp_lds_bytes(F, 4) <= kLdsBudget; }
 size_t linport_part_doubles(int nseg, int K) { return (size_t)nseg * 4 * linport_nv(K) * 16; }
 
+int linport_segments(const int* row_ptr, int T, std::vector<int>& seg, std::vector<int>& seg_ptr) {
+  seg.clear();
+  seg_ptr.assign((size_t)T + 1, 0);
+  for (int t = 0; t < T; ++t) {
+    for (int off = 0; off < row_ptr[t + 1] - row_ptr[t]; off += LINPORT_SEG) { seg.push_back(t); seg.push_back(off); }
+    seg_ptr[t + 1] = (int)(seg.size() / 2);
+  }
+  return (int)(seg.size() / 2);
+}
+
 void linport_pack_theta(const float* theta, int K, int F, float* packed) {
   const int NV = linport_nv(K), NS = 4 * lp_chunks(F);
   for (int s = 0; s < NS; ++s)
@@ -289,28 +299,28 @@ void linport_pack_theta(const float* theta, int K, int F, float* packed) {
 }
 
 static void linport_check(const LinportArgs& a, const char* what) {
-  if (a.F < 1 || a.F > 4096 || a.KP < 16 * lp_chunks(a.F) || a.T < 0 || a.nseg < 0 || a.T > 65535)
+  if (a.pv.F < 1 || a.pv.F > 4096 || a.pv.KP < 16 * lp_chunks(a.pv.F) || a.pv.T < 0 || a.nseg < 0 || a.pv.T > 65535)
     dlap_throw_hip(hipErrorInvalidValue, what, __FILE__, __LINE__);
 }
 
 void launch_managed(const LinportArgs& a, hipStream_t st) {
   linport_check(a, "managed: unsupported arguments");
-  if (a.T == 0 || a.nseg == 0) return;
-  const dim3 grid((unsigned)a.nseg, (unsigned)((a.F + 63) / 64));
-  if (a.fp32) hipLaunchKernelGGL((k_managed<true>), grid, dim3(kNT), 0, st, a);
+  if (a.pv.T == 0 || a.nseg == 0) return;
+  const dim3 grid((unsigned)a.nseg, (unsigned)((a.pv.F + 63) / 64));
+  if (a.pv.fp32) hipLaunchKernelGGL((k_managed<true>), grid, dim3(kNT), 0, st, a);
   else hipLaunchKernelGGL((k_managed<false>), grid, dim3(kNT), 0, st, a);
   HIP_OK(hipGetLastError());
-  hipLaunchKernelGGL(k_managed_reduce, dim3((unsigned)((a.T * a.F + kNT - 1) / kNT)), dim3(kNT), 0, st, a);
+  hipLaunchKernelGGL(k_managed_reduce, dim3((unsigned)((a.pv.T * a.pv.F + kNT - 1) / kNT)), dim3(kNT), 0, st, a);
   HIP_OK(hipGetLastError());
 }
 
 void launch_linport(const LinportArgs& a, hipStream_t st) {
   linport_check(a, "linport: unsupported arguments");
-  if (a.K < 1 || a.K > LINPORT_MAX_K || !a.theta || !linport_supported(a.F))
+  if (a.K < 1 || a.K > LINPORT_MAX_K || !a.theta || !linport_supported(a.pv.F))
     dlap_throw_hip(hipErrorInvalidValue, "linport: unsupported arguments", __FILE__, __LINE__);
-  if (a.T == 0 || a.nseg == 0) return;
+  if (a.pv.T == 0 || a.nseg == 0) return;
   const int NV = linport_nv(a.K);
-  if (a.fp32) linport_launch_nv<true>(a, NV, st);
+  if (a.pv.fp32) linport_launch_nv<true>(a, NV, st);
   else linport_launch_nv<false>(a, NV, st);
   HIP_OK(hipGetLastError());
 }

@@ -58,7 +58,7 @@ __global__ __launch_bounds__(QNT) void k_qsort_port(QsortArgs a) {
   // first key of the block and the number of its live columns
   const int k0 = is_char ? (int)blockIdx.x * QCB : a.C + ((int)blockIdx.x - cblocks) * QCB;
   const int nc = min(QCB, (is_char ? a.C : NK) - k0);
-  const int r0 = gp(a.row_ptr)[t], n = gp(a.row_ptr)[t + 1] - r0;
+  const int r0 = gp(a.pv.row_ptr)[t], n = gp(a.pv.row_ptr)[t + 1] - r0;
   const size_t ob = (size_t)t * NK + k0;               // outputs of the block's columns are adjacent
   if (n <= 0) {                                        // empty period: no row is read
     for (int i = tid; i < nc * Q; i += QNT) gp(a.count)[ob * Q + i] = 0;
@@ -68,7 +68,7 @@ __global__ __launch_bounds__(QNT) void k_qsort_port(QsortArgs a) {
   }
   const bool live = c < nc;
   const int col = is_char && live ? (a.cols ? gp(a.cols)[k0 + c] : k0 + c) : 0;
-  const float* ext = !is_char && live ? a.extra + ((size_t)(k0 + c - a.C) * a.T + t) * a.N : nullptr;
+  const float* ext = !is_char && live ? a.extra + ((size_t)(k0 + c - a.C) * a.pv.T + t) * a.pv.N : nullptr;
 
   __shared__ double red[QNT / 64 * QCB * QSORT_MAX_Q * QMAXV];     // 20 480 B, first the histograms
   uint32_t* hist = reinterpret_cast<uint32_t*>(red);               // [QCB][QHC]
@@ -108,7 +108,7 @@ __global__ __launch_bounds__(QNT) void k_qsort_port(QsortArgs a) {
 #pragma unroll
         for (int k = 0; k < QUC; ++k) {
           const int j = j0 + k * QRS;
-          u[k] = j < n ? qkey_load<F32>(a, is_char, col, ext, r0 + j) : 0u;
+          u[k] = j < n ? qkey_load<F32>(a.pv, is_char, col, ext, r0 + j) : 0u;
         }
 #pragma unroll
         for (int k = 0; k < QUC; ++k) {
@@ -171,12 +171,12 @@ __global__ __launch_bounds__(QNT) void k_qsort_port(QsortArgs a) {
       for (int k = 0; k < QUA; ++k) {
         const int j = j0 + k * QRS, r = r0 + j;
         const bool in = j < n;
-        u[k] = in ? qkey_load<F32>(a, is_char, col, ext, r) : 0u;
-        val[k][0] = in ? gp(a.Rc)[r] : 0.f;
+        u[k] = in ? qkey_load<F32>(a.pv, is_char, col, ext, r) : 0u;
+        val[k][0] = in ? gp(a.pv.Rc)[r] : 0.f;
         if constexpr (K1 > 1) {
-          const int i = in ? gp(a.rowti)[r].y : 0;
+          const int i = in ? gp(a.pv.rowti)[r].y : 0;
 #pragma unroll
-          for (int v = 1; v < K1; ++v) val[k][v] = in ? gp(a.values)[((size_t)(v - 1) * a.T + t) * a.N + i] : 0.f;
+          for (int v = 1; v < K1; ++v) val[k][v] = in ? gp(a.values)[((size_t)(v - 1) * a.pv.T + t) * a.pv.N + i] : 0.f;
         }
       }
 #pragma unroll
@@ -232,12 +232,12 @@ static void qsort_launch_k(const QsortArgs& a, dim3 grid, hipStream_t st) {
 }
 
 void launch_qsort_port(const QsortArgs& a, hipStream_t st) {
-  if (a.Q < 2 || a.Q > QSORT_MAX_Q || a.K < 0 || a.K > QSORT_MAX_VALUES || a.C < 0 || a.E < 0 || a.T > 65535 ||
+  if (a.Q < 2 || a.Q > QSORT_MAX_Q || a.K < 0 || a.K > QSORT_MAX_VALUES || a.C < 0 || a.E < 0 || a.pv.T > 65535 ||
       (a.E > 0 && !a.extra) || (a.K > 0 && !a.values))
     dlap_throw_hip(hipErrorInvalidValue, "qsort_port: unsupported arguments", __FILE__, __LINE__);
-  if (a.T <= 0 || a.C + a.E <= 0) return;
-  const dim3 grid((unsigned)((a.C + QCB - 1) / QCB + (a.E + QCB - 1) / QCB), (unsigned)a.T);
-  if (a.fp32) qsort_launch_k<true>(a, grid, st);
+  if (a.pv.T <= 0 || a.C + a.E <= 0) return;
+  const dim3 grid((unsigned)((a.C + QCB - 1) / QCB + (a.E + QCB - 1) / QCB), (unsigned)a.pv.T);
+  if (a.pv.fp32) qsort_launch_k<true>(a, grid, st);
   else qsort_launch_k<false>(a, grid, st);
   HIP_OK(hipGetLastError());
 }

@@ -69,7 +69,7 @@ template <bool F32, int K1>
 __global__ __launch_bounds__(Q2NT) void k_qsort2_port(Qsort2Args a) {
   const int p = blockIdx.x, t = blockIdx.y, Qa = a.Qa, Qb = a.Qb, nba = Qa - 1, nbb = Qb - 1, nc = Qa * Qb;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int r0 = gp(a.row_ptr)[t], n = gp(a.row_ptr)[t + 1] - r0;
+  const int r0 = gp(a.pv.row_ptr)[t], n = gp(a.pv.row_ptr)[t + 1] - r0;
   const size_t ob = (size_t)t * a.P + p;
   const float qnan = __uint_as_float(0x7FC00000u);
   if (n <= 0) {                                        // empty period: no row is read
@@ -80,10 +80,10 @@ __global__ __launch_bounds__(Q2NT) void k_qsort2_port(Qsort2Args a) {
     return;
   }
   const int2 pr = gp(a.pairs)[p];
-  const bool charA = pr.x < a.F, charB = pr.y < a.F;
+  const bool charA = pr.x < a.pv.F, charB = pr.y < a.pv.F;
   const int colA = charA ? pr.x : 0, colB = charB ? pr.y : 0;
-  const float* extA = charA ? nullptr : a.extra + ((size_t)(pr.x - a.F) * a.T + t) * a.N;
-  const float* extB = charB ? nullptr : a.extra + ((size_t)(pr.y - a.F) * a.T + t) * a.N;
+  const float* extA = charA ? nullptr : a.extra + ((size_t)(pr.x - a.pv.F) * a.pv.T + t) * a.pv.N;
+  const float* extB = charB ? nullptr : a.extra + ((size_t)(pr.y - a.pv.F) * a.pv.T + t) * a.pv.N;
   const bool k16A = !F32 && charA, k16B = !F32 && charB;
   const int lowA = k16A ? 16 : 0, lowB = k16B ? 16 : 0;   // the keys' lowest significant bits
   const bool cond = a.conditional != 0;
@@ -129,8 +129,8 @@ __global__ __launch_bounds__(Q2NT) void k_qsort2_port(Qsort2Args a) {
 #pragma unroll
         for (int k = 0; k < Q2UC; ++k) {
           const int j = j0 + k * Q2NT;
-          u[k] = j < n ? qkey_load<F32>(a, kchar, kcol, kext, r0 + j) : 0u;
-          ua[k] = cnd && j < n ? qkey_load<F32>(a, charA, colA, extA, r0 + j) : 0u;
+          u[k] = j < n ? qkey_load<F32>(a.pv, kchar, kcol, kext, r0 + j) : 0u;
+          ua[k] = cnd && j < n ? qkey_load<F32>(a.pv, charA, colA, extA, r0 + j) : 0u;
         }
 #pragma unroll
         for (int k = 0; k < Q2UC; ++k) {
@@ -227,13 +227,13 @@ __global__ __launch_bounds__(Q2NT) void k_qsort2_port(Qsort2Args a) {
     for (int k = 0; k < Q2UC; ++k) {
       const int j = j0 + tid + k * Q2NT, r = r0 + j;
       const bool in = j < n;
-      ua[k] = in ? qkey_load<F32>(a, charA, colA, extA, r) : 0u;
-      ub[k] = in ? qkey_load<F32>(a, charB, colB, extB, r) : 0u;
-      val[k][0] = in ? gp(a.Rc)[r] : 0.f;
+      ua[k] = in ? qkey_load<F32>(a.pv, charA, colA, extA, r) : 0u;
+      ub[k] = in ? qkey_load<F32>(a.pv, charB, colB, extB, r) : 0u;
+      val[k][0] = in ? gp(a.pv.Rc)[r] : 0.f;
       if constexpr (K1 > 1) {
-        const int i = in ? gp(a.rowti)[r].y : 0;
+        const int i = in ? gp(a.pv.rowti)[r].y : 0;
 #pragma unroll
-        for (int v = 1; v < K1; ++v) val[k][v] = in ? gp(a.values)[((size_t)(v - 1) * a.T + t) * a.N + i] : 0.f;
+        for (int v = 1; v < K1; ++v) val[k][v] = in ? gp(a.values)[((size_t)(v - 1) * a.pv.T + t) * a.pv.N + i] : 0.f;
       }
     }
 #pragma unroll
@@ -287,12 +287,12 @@ static void qsort2_launch_k(const Qsort2Args& a, dim3 grid, hipStream_t st) {
 
 void launch_qsort2_port(const Qsort2Args& a, hipStream_t st) {
   if (a.Qa < 2 || a.Qa > QSORT2_MAX_Q || a.Qb < 2 || a.Qb > QSORT2_MAX_Q || a.Qa * a.Qb > QSORT2_MAX_CELLS ||
-      a.K < 0 || a.K > QSORT2_MAX_VALUES || a.P < 0 || a.E < 0 || a.F < 0 || a.T > 65535 ||
+      a.K < 0 || a.K > QSORT2_MAX_VALUES || a.P < 0 || a.E < 0 || a.pv.F < 0 || a.pv.T > 65535 ||
       (a.P > 0 && !a.pairs) || (a.E > 0 && !a.extra) || (a.K > 0 && !a.values))
     dlap_throw_hip(hipErrorInvalidValue, "qsort2_port: unsupported arguments", __FILE__, __LINE__);
-  if (a.T <= 0 || a.P <= 0) return;
-  const dim3 grid((unsigned)a.P, (unsigned)a.T);
-  if (a.fp32) qsort2_launch_k<true>(a, grid, st);
+  if (a.pv.T <= 0 || a.P <= 0) return;
+  const dim3 grid((unsigned)a.P, (unsigned)a.pv.T);
+  if (a.pv.fp32) qsort2_launch_k<true>(a, grid, st);
   else qsort2_launch_k<false>(a, grid, st);
   HIP_OK(hipGetLastError());
 }

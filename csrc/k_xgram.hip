@@ -87,8 +87,8 @@ __global__ __launch_bounds__(kNT) void k_xgram(XgramArgs a) {
   int* s_slot = tab + kSlots;                                   // [waves][kFr] slot of a wave's fragment
   const int tid = threadIdx.x, lane = tid & 63, q = lane >> 4, n = lane & 15;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int t = blockIdx.x, F = a.F, NB = (F + 15) >> 4;
-  const int r0 = gp(a.row_ptr)[t], cnt = gp(a.row_ptr)[t + 1] - r0;
+  const int t = blockIdx.x, F = a.pv.F, NB = (F + 15) >> 4;
+  const int r0 = gp(a.pv.row_ptr)[t], cnt = gp(a.pv.row_ptr)[t + 1] - r0;
 
   if (tid == 0) {                 // the column blocks of the four super-tiles, each listed once
     int nn = 0;
@@ -154,14 +154,14 @@ __global__ __launch_bounds__(kNT) void k_xgram(XgramArgs a) {
         const int j = rem / CPB, h = rem - j * CPB;
         const int col0 = s_blk[j] * 16 + h * (F32 ? 4 : 8);
         const bool live = k0 + row < runlen;
-        const size_t src = (size_t)(r0 + run0 + (live ? k0 + row : 0)) * a.KP + col0;   // (a dead row re-reads a live one)
+        const size_t src = (size_t)(r0 + run0 + (live ? k0 + row : 0)) * a.pv.KP + col0;   // (a dead row re-reads a live one)
         u32x4 v;
         if constexpr (F32) {
-          v = *reinterpret_cast<const DLAP_GLOBAL u32x4*>(gp(reinterpret_cast<const float*>(a.X)) + src);
+          v = *reinterpret_cast<const DLAP_GLOBAL u32x4*>(gp(reinterpret_cast<const float*>(a.pv.X)) + src);
 #pragma unroll
           for (int e = 0; e < 4; ++e) v[e] = live && col0 + e < F ? v[e] : 0u;
         } else {
-          v = *reinterpret_cast<const DLAP_GLOBAL u32x4*>(gp(reinterpret_cast<const u16*>(a.X)) + src);
+          v = *reinterpret_cast<const DLAP_GLOBAL u32x4*>(gp(reinterpret_cast<const u16*>(a.pv.X)) + src);
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
             const uint32_t m = (live && col0 + 2 * e < F ? 0xFFFFu : 0u) | (live && col0 + 2 * e + 1 < F ? 0xFFFF0000u : 0u);
@@ -216,7 +216,7 @@ __global__ __launch_bounds__(kNT) void k_xgram(XgramArgs a) {
   if (blockIdx.y == 0) {
     double pr = 0.0, prr = 0.0;
     for (int j = tid; j < cnt; j += kNT) {
-      const double R = (double)gp(a.Rc)[r0 + j];
+      const double R = (double)gp(a.pv.Rc)[r0 + j];
       pr += R;
       prr += R * R;
     }
@@ -231,7 +231,7 @@ __global__ __launch_bounds__(kNT) void k_xgram(XgramArgs a) {
       double s = red[tid * kWaves];
 #pragma unroll
       for (int k = 1; k < kWaves; ++k) s += red[tid * kWaves + k];
-      gp(a.sum_r)[(size_t)tid * a.T + t] = s;
+      gp(a.sum_r)[(size_t)tid * a.pv.T + t] = s;
     }
     if (tid == 2) gp(a.n)[t] = cnt;
   }
@@ -251,12 +251,12 @@ void xgram_tiles(int F, std::vector<int>& tiles) {
 }
 
 void launch_xgram(const XgramArgs& a, hipStream_t st) {
-  const int NB = (a.F + 15) / 16;
-  if (a.F < 1 || a.F > 4096 || a.KP < 16 * NB || a.KP % 16 != 0 || a.T < 0 || a.T > 65535 || a.ntiles < 1 || !a.tiles)
+  const int NB = (a.pv.F + 15) / 16;
+  if (a.pv.F < 1 || a.pv.F > 4096 || a.pv.KP < 16 * NB || a.pv.KP % 16 != 0 || a.pv.T < 0 || a.pv.T > 65535 || a.ntiles < 1 || !a.tiles)
     dlap_throw_hip(hipErrorInvalidValue, "xgram: unsupported arguments", __FILE__, __LINE__);
-  if (a.T == 0) return;
-  const dim3 grid((unsigned)a.T, (unsigned)((a.ntiles + kWaves - 1) / kWaves));
-  if (a.fp32) hipLaunchKernelGGL((k_xgram<true>), grid, dim3(kNT), lds_bytes<true>(), st, a);
+  if (a.pv.T == 0) return;
+  const dim3 grid((unsigned)a.pv.T, (unsigned)((a.ntiles + kWaves - 1) / kWaves));
+  if (a.pv.fp32) hipLaunchKernelGGL((k_xgram<true>), grid, dim3(kNT), lds_bytes<true>(), st, a);
   else hipLaunchKernelGGL((k_xgram<false>), grid, dim3(kNT), lds_bytes<false>(), st, a);
   HIP_OK(hipGetLastError());
 }

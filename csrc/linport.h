@@ -2,8 +2,8 @@
 // of a split and the per-period sums of up to LINPORT_MAX_K linear portfolios w = x . theta_k.
 // Shared with the engine. analysis/benchmarks.py holds the definitions (numpy, the oracle).
 //
-// Both kernels read the compacted rows X [R][KP], Rc and row_ptr only (k_linport also rowti when
-// it writes the dense weights), so they run for every engine shape. A period is cut into
+// Both kernels read the resident panel only (panel_view.h: X, Rc and row_ptr; k_linport also rowti
+// when it writes the dense weights), so they run for every engine shape. A period is cut into
 // segments of LINPORT_SEG rows (a constant: the partition depends on row_ptr alone); a workgroup
 // owns one segment, and the segments of a period are added in index order by a second small
 // launch. fp64 sums, no float atomics: repeated calls are bitwise identical.
@@ -17,22 +17,21 @@
 //               sums describe exactly the fp32 values written to w_out (S1 - n c = sum v); with
 //               c = 0 it is sum w.
 #pragma once
+#include <vector>
 #include "common.h"
+#include "panel_view.h"
 
 #define LINPORT_MAX_K 64
-#ifndef LINPORT_SEG             // (-DLINPORT_SEG=n on k_linport.hip and engine.cpp: a side build for A/B runs)
-#define LINPORT_SEG 512         // rows per segment (32 MFMA row tiles; measured against 256 and 1024,
-#endif                          // profiles/linear_benchmarks_timing.txt)
+// Rows per segment (32 MFMA row tiles; measured against 256 and 1024,
+// profiles/linear_benchmarks_timing.txt). A side build for A/B runs sets -DLINPORT_SEG=n on
+// k_linport.hip and k_pred.hip, the two files that compile it in; the engine asks linport_segments.
+#ifndef LINPORT_SEG
+#define LINPORT_SEG 512
+#endif
 
 struct LinportArgs {
-  // the split's compacted panel (engine layout)
-  const void* X;          // [R][KP] bf16 bits, or fp32 when fp32 != 0; columns >= F are not read as data
-  int KP, fp32, F;
-  const float* Rc;        // [R]
-  const int2* rowti;      // [R] (t, i)
-  const int* row_ptr;     // [T+1]
-  int T, N;
-  // segments (host-built from row_ptr): seg[j] = (period, first row of the segment within it),
+  PanelView pv;           // the split's compacted panel (panel_view.h)
+  // segments (linport_segments): seg[j] = (period, first row of the segment within it),
   // seg_ptr[t] .. seg_ptr[t+1] the segments of period t
   const int2* seg;
   const int* seg_ptr;
@@ -59,6 +58,9 @@ void linport_pack_theta(const float* theta, int K, int F, float* packed);
 // true when the fragments of an F-column theta fit the LDS of a workgroup
 bool linport_supported(int F);
 size_t linport_part_doubles(int nseg, int K);
+// The segment table of a split from the host copy of row_ptr [T+1], cut as k_linport.hip was
+// compiled: seg = (period, first row within it) pairs, seg_ptr [T+1]. Returns the number of segments.
+int linport_segments(const int* row_ptr, int T, std::vector<int>& seg, std::vector<int>& seg_ptr);
 
 // T == 0 or nseg == 0 launches nothing (the caller's zero-filled results stand).
 void launch_managed(const LinportArgs& a, hipStream_t st);

@@ -8,18 +8,13 @@
 // Tied keys share the lowest bucket any of them would get.
 #pragma once
 #include "common.h"
+#include "panel_view.h"
 
 #define QSORT_MAX_Q 16
 #define QSORT_MAX_VALUES 4      // caller-supplied value columns (value 0 is the split's return)
 
 struct QsortArgs {
-  // the split's compacted panel (engine layout)
-  const void* X;          // [R][KP] bf16 bits, or fp32 when fp32 != 0; columns [0, F) are the characteristics
-  int KP, fp32;
-  const float* Rc;        // [R] returns of the compact rows
-  const int2* rowti;      // [R] (t, i)
-  const int* row_ptr;     // [T+1] first compact row of each period
-  int T, N;
+  PanelView pv;           // the split's compacted panel (panel_view.h)
   // keys: C characteristic columns (cols[k], or k when cols is null), then E dense arrays
   int Q;                  // buckets, 2 .. QSORT_MAX_Q
   int C;

@@ -11,21 +11,15 @@
 // Tied keys share the lowest bucket any of them would get, in both dimensions.
 #pragma once
 #include "common.h"
+#include "panel_view.h"
 
 #define QSORT2_MAX_Q 16
 #define QSORT2_MAX_CELLS 36     // Qa * Qb
 #define QSORT2_MAX_VALUES 2     // caller-supplied value columns (value 0 is the split's return)
 
 struct Qsort2Args {
-  // the split's compacted panel (engine layout)
-  const void* X;          // [R][KP] bf16 bits, or fp32 when fp32 != 0; columns [0, F) are the characteristics
-  int KP, fp32;
-  const float* Rc;        // [R] returns of the compact rows
-  const int2* rowti;      // [R] (t, i)
-  const int* row_ptr;     // [T+1] first compact row of each period
-  int T, N;
-  // keys: index k < F is panel column k, index F + e the dense array e of extra
-  int F;
+  PanelView pv;           // the split's compacted panel (panel_view.h)
+  // keys: index k < pv.F is panel column k, index pv.F + e the dense array e of extra
   int P;                  // pairs
   const int2* pairs;      // device [P] (A, B) key indices in [0, F + E)
   int Qa, Qb;             // 2 .. QSORT2_MAX_Q each, Qa * Qb <= QSORT2_MAX_CELLS

@@ -2,6 +2,7 @@
 // order-preserving float -> uint32 key map and the key load from the compacted panel.
 #pragma once
 #include "common.h"
+#include "panel_view.h"
 
 DLAP_DEV uint32_t qkey_u32(float x) {
   uint32_t b = __float_as_uint(x);
@@ -15,9 +16,8 @@ DLAP_DEV float qkey_f32(uint32_t u, bool k16) {
 }
 
 // key of compact row r: panel column col of a characteristic block, else the dense array ext [N]
-// (Args: QsortArgs or Qsort2Args, which name the panel fields alike)
-template <bool F32, class Args>
-DLAP_DEV uint32_t qkey_load(const Args& a, bool is_char, int col, const float* ext, int r) {
+template <bool F32>
+DLAP_DEV uint32_t qkey_load(const PanelView& a, bool is_char, int col, const float* ext, int r) {
   if (is_char) {
     if constexpr (F32) return qkey_u32(gp(reinterpret_cast<const float*>(a.X))[(size_t)r * a.KP + col]);
     else {

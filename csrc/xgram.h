@@ -5,8 +5,8 @@
 // Per period t of a split, over its valid rows, with x as the engine stores it:
 //   gram[t][a][b] = sum_i x[i][a] x[i][b]  (a, b < F),  sum_r[t] = sum R,  sum_rr[t] = sum R^2,
 //   n[t] from row_ptr.
-// The kernel reads X [R][KP], Rc and row_ptr only, so it runs for every engine shape (fused and
-// wide layer-0 path, bf16 and fp32 panel) and needs no model.
+// The kernel reads the resident panel only (panel_view.h: X, Rc and row_ptr), so it runs for every
+// engine shape (fused and wide layer-0 path, bf16 and fp32 panel) and needs no model.
 //
 // Determinism. A period is cut into runs of XGRAM_RUN consecutive rows counted from its first row
 // (the partition depends on row_ptr alone). gram[t] is the sum, in run order, of the fp32 Gram of
@@ -19,6 +19,7 @@
 #pragma once
 #include <vector>
 #include "common.h"
+#include "panel_view.h"
 
 #ifndef XGRAM_RUN               // (-DXGRAM_RUN=n on k_xgram.hip: a side build for A/B runs; the engine
 #define XGRAM_RUN 128           // asks xgram_run()) rows per fp32 run: a multiple of 32, <= 512 (measured
@@ -26,12 +27,7 @@
 static_assert(XGRAM_RUN >= 32 && XGRAM_RUN <= 512 && XGRAM_RUN % 32 == 0, "XGRAM_RUN: a multiple of 32 in [32, 512]");
 
 struct XgramArgs {
-  // the split's compacted panel (engine layout)
-  const void* X;          // [R][KP] bf16 bits, or fp32 when fp32 != 0; columns >= F are not read as data
-  int KP, fp32, F;
-  const float* Rc;        // [R]
-  const int* row_ptr;     // [T+1]
-  int T;
+  PanelView pv;           // the split's compacted panel (panel_view.h; rowti and N are not read)
   // super-tiles (xgram_tiles): (ia, ib) = feature blocks 2 ia, 2 ia + 1 against 4 ib .. 4 ib + 3
   const int2* tiles;
   int ntiles;
