@@ -17,9 +17,16 @@
 //    (ds_read_b64_tr_b16): the wave writes a packed activation / dz / panel fragment set into a
 //    32-row x 64-column bf16 image and reads it back column-major -- no selector MFMAs, no
 //    conversions; the image rows are 128 B with the four 32-byte column chunks XOR-swizzled by row
-//    bits 1 and 3, so a transposed read is bank-conflict free;
-//  * the next two tiles' panel rows, periods, dL/dw and keep words are in flight in registers
-//    (three slots, the tile loop unrolled by three so no slot is ever copied);
+//    bits 1 and 3, which by construction spreads a transposed read over 64 distinct banks (img_off).
+//    The counters still show about 130 LDS bank-conflict cycles per tile (1016 per wave at the
+//    bench shape, before and after the tile-loop rework): the T-fragment writes are 2-way by
+//    design (24 per tile at two layers); which access gives the rest has not been measured;
+//  * the next two tiles' panel rows, periods, dL/dw and keep words are in flight in registers: two
+//    slots -- a tile's slot is dead once its rows are in the image, so the slot behind it moves
+//    down there (one copy per tile) and the tile two ahead is issued (see the tile loop);
+//  * the backward's packed ReLU / keep / gate forms (PrecBF16B), the staging with every load in
+//    flight before the first wait and the DPP row sums of the epilogue: what each gave is in
+//    profiles/tbwd_issue_after.txt;
 //  * the four waves' partial gradients are combined in a fixed tree ((w0 + w1) + (w2 + w3)) through
 //    LDS and stored as the workgroup's slab in the layout k_finalize / k_lstm_tail read (tile t of
 //    layer t at t * 4096 + 64 o + i, the extra rows after NL * 4096): the fine-slab partition
@@ -141,6 +148,45 @@ DLAP_DEV void acc_fence4(f32x4& a0, f32x4& a1, f32x4& a2, f32x4& a3) {
   asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 7" : "+a"(a0), "+a"(a1), "+a"(a2), "+a"(a3));
 }
 
+// The backward's own forms of PrecBF16's packed activation and gate: the same bits, one VALU
+// instruction less per dword each (the forward kernels keep the shared forms of common.h).
+//  * act (4 instead of 5): instead of a 0xFFFF / 0 keep mask (shift, arithmetic shift, and), the
+//    DROP bit -- of the inverted keep word, inverted once per word -- is shifted to the sign bit of
+//    each half and or-ed into the converted pair (one v_and_or_b32): the ReLU's signed max then
+//    zeroes the dropped elements along with the negative ones; a kept element is untouched;
+//  * gate (3 instead of 4): the recomputed activation a is a non-negative bf16 (0x0000 .. 0x7FFF
+//    per half), so min_u16(a, 1) is 1 where a != 0; the converted pair is multiplied by it.
+struct PrecBF16B : PrecBF16 {
+  template <int SH>
+  DLAP_DEV static uint32_t or_drop_sign(uint32_t nkw, uint32_t v) {
+    uint32_t t;      // (op_sel_hi:[0,1]: both halves shift by the constant's low 16 bits, see keep_mask)
+    asm("v_pk_lshlrev_b16 %0, %1, %2 op_sel_hi:[0,1]" : "=v"(t) : "i"(15 - SH), "v"(nkw));
+    return (t & 0x80008000u) | v;
+  }
+  template <int BS, bool DROP>
+  DLAP_DEV static Frag act(const f32x4& lo, const f32x4& hi, uint32_t kw) {
+    u32x4 v{cvt_pk(lo[0], lo[1]), cvt_pk(lo[2], lo[3]), cvt_pk(hi[0], hi[1]), cvt_pk(hi[2], hi[3])};
+    if constexpr (DROP) {
+      const uint32_t nkw = ~kw;
+      v[0] = or_drop_sign<BS + 0>(nkw, v[0]); v[1] = or_drop_sign<BS + 1>(nkw, v[1]);
+      v[2] = or_drop_sign<BS + 2>(nkw, v[2]); v[3] = or_drop_sign<BS + 3>(nkw, v[3]);
+    }
+    return __builtin_bit_cast(Frag, u32x4{relu_pk(v[0]), relu_pk(v[1]), relu_pk(v[2]), relu_pk(v[3])});
+  }
+  DLAP_DEV static uint32_t gate_pk(uint32_t d, uint32_t a) {
+    uint32_t nz, r;  // (asm: hipcc rewrites the plain C form into compares, selects and a v_perm;
+                     //  op_sel_hi:[1,0]: the high half also compares with the constant's low 16 bits)
+    asm("v_pk_min_u16 %0, %1, 1 op_sel_hi:[1,0]" : "=v"(nz) : "v"(a));
+    asm("v_pk_mul_lo_u16 %0, %1, %2" : "=v"(r) : "v"(d), "v"(nz));
+    return r;
+  }
+  DLAP_DEV static Frag gate(const f32x4& lo, const f32x4& hi, const Frag& a) {
+    const u32x4 av = __builtin_bit_cast(u32x4, a);
+    return __builtin_bit_cast(Frag, u32x4{gate_pk(cvt_pk(lo[0], lo[1]), av[0]), gate_pk(cvt_pk(lo[2], lo[3]), av[1]),
+                                          gate_pk(cvt_pk(hi[0], hi[1]), av[2]), gate_pk(cvt_pk(hi[2], hi[3]), av[3])});
+  }
+};
+
 __host__ __device__ inline size_t tb_img_base(const MlpDims& D) { return (lds_bytes_of(D) + 15) & ~(size_t)15; }
 // (the launch's D has the per-period inputs staged: pp_lds_floats = T * ppst)
 size_t tb_lds_bytes(const MlpDims& D) {
@@ -243,11 +289,13 @@ struct TbState {
 // ZIN (wide path): the tile input is the stored layer-0 pre-activation z (k_mlp_fwd_zx), layer 0's
 // gradient tile covers only the per-period input columns W0[:, F:F+Dm] (the panel columns are
 // k_wgrad0's), and the layer-0 dz is stored for k_wgrad0 (J.dz_out [tile][4][64]).
-template <int NL, bool ZIN, class TI>
+// `consumed()` runs once the tile's prefetch slot `in` is dead (the caller refills it there).
+template <int NL, bool ZIN, class TI, class CONS>
 DLAP_DEV void tb_tile(const MlpJob& J, const MlpDims& D, const TbW<NL, kTbRes<NL>>& W, const float* aux, const float* spp,
                       char* img, const ImgMap& im, int tile, TI& in, const uint32_t (&kw)[NL],
-                      TbState<NL>& S) {
+                      TbState<NL>& S, CONS&& consumed) {
   using P = PrecBF16;
+  using PB = PrecBF16B;                                  // (the packed activation / gate forms)
   using Frag = bf16x8;
   const int lane = lane_id(), q = lane >> 4;
   const float* auxt = aux;
@@ -256,6 +304,7 @@ DLAP_DEV void tb_tile(const MlpJob& J, const MlpDims& D, const TbW<NL, kTbRes<NL
   char* zimg = img + 2 * kImg;
   Frag xf[2][2];
   f32x4 a[2][4];
+  float dw0, dw1;
   if constexpr (ZIN) {
     const RowInfo ri = finish_ztile<1>(J, tile, in);       // dw = 0 beyond R
 #pragma unroll
@@ -266,9 +315,14 @@ DLAP_DEV void tb_tile(const MlpJob& J, const MlpDims& D, const TbW<NL, kTbRes<NL
     img_put_x(ximg, im, xf);
     __builtin_amdgcn_sched_barrier(0);
     zin_sdf0(in.zs, ri, spp, D.ppst, auxt, D, a);
+    dw0 = in.dw[0]; dw1 = in.dw[1];
+    consumed();
+    __builtin_amdgcn_sched_barrier(0);
   } else {
     tb_finish(J, D, tile, in, xf, spp);                  // per-period columns inserted; dw = 0 beyond R
     img_put_x(ximg, im, xf);
+    dw0 = in.dw[0]; dw1 = in.dw[1];
+    consumed();
     __builtin_amdgcn_sched_barrier(0);
     // ---- forward recompute (the train blob: dropout scale folded into layers >= 1) ----
 #pragma unroll
@@ -285,15 +339,14 @@ DLAP_DEV void tb_tile(const MlpJob& J, const MlpDims& D, const TbW<NL, kTbRes<NL
     }
   }
   Frag act[NL][2][2];
-  act_tile<P, 4, true>(a, kw[0], act[0]);
+  act_tile<PB, 4, true>(a, kw[0], act[0]);
 #pragma unroll
   for (int j = 1; j < NL; ++j) {
     tb_chain([&](int k) { return W.wf(j - 1, k); }, act[j - 1], a, auxt + D.a_sb + 64 * j);
-    act_tile<P, 4, true>(a, kw[j], act[j]);
+    act_tile<PB, 4, true>(a, kw[j], act[j]);
     __builtin_amdgcn_sched_barrier(0);
   }
   // ---- output layer: dz = dw * wo' gated by the last activation; output-row / bias sums ----
-  const float dw0 = in.dw[0], dw1 = in.dw[1];
   Frag dzf[2][2];
   {
     f32x4 t[2][4];
@@ -303,7 +356,7 @@ DLAP_DEV void tb_tile(const MlpJob& J, const MlpDims& D, const TbW<NL, kTbRes<NL
       t[0][u] = dw0 * ww;
       t[1][u] = dw1 * ww;
     }
-    gate_tile<P, 4>(t, act[NL - 1], dzf);
+    gate_tile<PB, 4>(t, act[NL - 1], dzf);
   }
 #pragma unroll
   for (int b = 0; b < 2; ++b)
@@ -318,6 +371,10 @@ DLAP_DEV void tb_tile(const MlpJob& J, const MlpDims& D, const TbW<NL, kTbRes<NL
   S.gbo += q == 0 ? dw0 + dw1 : 0.f;
   __builtin_amdgcn_sched_barrier(0);
   // ---- backward chain: layer j's weight / bias gradients, then dz of layer j - 1 ----
+  // (Issuing the chain to layer j - 1, which needs only dzf, between the transposed reads and the
+  // MFMAs that use them -- to cover the operands' LDS round trip -- measured no faster: the eight
+  // operand fragments then live across the chain and cost some 40 more register moves per tile;
+  // profiles/tbwd_issue_after.txt.)
 #pragma unroll
   for (int j = NL - 1; j >= 0; --j) {
     img_put_t(zimg, im, dzf);
@@ -350,7 +407,7 @@ DLAP_DEV void tb_tile(const MlpJob& J, const MlpDims& D, const TbW<NL, kTbRes<NL
     if (j > 0) {
       f32x4 da[2][4];
       tb_chain([&](int k) { return W.wb(j - 1, k); }, dzf, da, nullptr);
-      gate_tile<P, 4>(da, act[j - 1], dzf);
+      gate_tile<PB, 4>(da, act[j - 1], dzf);
     } else if (D.nrnn > 0) {
       // dL/d(per-period input d) per row = sum_out W0[out][F + d] dz0[out][row] (d < Dm <= 16)
       f32x4 c[2];
@@ -360,17 +417,86 @@ DLAP_DEV void tb_tile(const MlpJob& J, const MlpDims& D, const TbW<NL, kTbRes<NL
 #pragma unroll
         for (int s = 0; s < 2; ++s) c[b] = P::mma(W.wpp(s), dzf[b][s], c[b]);
       }
+      // (Dm a multiple of 4 -- the production LSTM width: a lane's four are one aligned 16-byte
+      // store under one predicate, not four stores under a branch each; u_out is an allocation of
+      // its own)
+      const bool v4 = (D.Dm & 3) == 0;
 #pragma unroll
       for (int b = 0; b < 2; ++b) {
         const int row = tile * 32 + 16 * b + (lane & 15);
+        if (v4) {
+          if (4 * q < D.Dm && row < J.R)
+            *(DLAP_GLOBAL f32x4*)gp32(J.u_out, (uint32_t)(row * D.Dm + 4 * q)) = c[b];
+        } else {
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int d = 4 * q + r;
-          if (d < D.Dm && row < J.R) *gp32(J.u_out, (uint32_t)(row * D.Dm + d)) = c[b][r];
+          for (int r = 0; r < 4; ++r) {
+            const int d = 4 * q + r;
+            if (d < D.Dm && row < J.R) *gp32(J.u_out, (uint32_t)(row * D.Dm + d)) = c[b][r];
+          }
         }
       }
     }
   }
+}
+
+// The prologue's staging (stage_weights of tower_dev.h, for this kernel): the blob by LDS-DMA, aux
+// and the zero-padded per-period inputs by plain loads -- with the first batch of BOTH issued before
+// anything waits (stage_weights waits for its aux batch, then for its per-period batch: two more
+// serial round trips behind the job's), `in_flight()` (register setup that needs no memory) run
+// under them, and one division per thread for the padded rows instead of one per element. At the
+// production sizes (aux <= 2048 floats, T * ppst <= 2048) the first batch is all there is.
+template <typename F>
+DLAP_DEV void tb_stage(const MlpJob& J, const MlpDims& D, bf16x8* lds, float* aux, float* spp, F&& in_flight) {
+  const int n16 = D.blob_frags * 64;                                // 16-byte pieces
+  const auto src = reinterpret_cast<const DLAP_GLOBAL int4*>(gp(J.blob));
+  int4* l16 = reinterpret_cast<int4*>(lds);
+  const int lane = threadIdx.x & 63;
+  for (int i = threadIdx.x; i < n16; i += blockDim.x)
+    __builtin_amdgcn_global_load_lds(src + i, (LDS3 void*)(l16 + (i - lane)), 16, 0, 0);
+  constexpr int B = 8;
+  const int nthr = blockDim.x;
+  const auto ga = gp(J.aux);
+  const auto gpp = gp(J.pp);
+  const int n = (D.pp_lds_floats > 0 && D.Dm > 0) ? J.T * D.ppst : 0;
+  // element i = threadIdx.x + k * nthr of the padded rows is (t, c); a step of nthr elements is
+  // (dt, dc) with a carry
+  // (pst: no per-period inputs, no rows -- and no division by zero)
+  const int pst = max(D.ppst, 1);
+  const int dt = nthr / pst, dc = nthr - dt * pst;
+  int t = (int)threadIdx.x / pst, c = (int)threadIdx.x - t * pst;
+  float va[B], vp[B];
+#pragma unroll
+  for (int k = 0; k < B; ++k) {
+    const int i = threadIdx.x + k * nthr;
+    va[k] = ga[i < D.aux_floats ? i : 0];
+  }
+#pragma unroll
+  for (int k = 0; k < B; ++k) {
+    const int i = threadIdx.x + k * nthr;
+    vp[k] = (i < n && c < D.Dm) ? gpp[t * D.Dm + c] : 0.f;
+    t += dt; c += dc;
+    if (c >= pst) { c -= pst; ++t; }
+  }
+  in_flight();
+#pragma unroll
+  for (int k = 0; k < B; ++k) {
+    const int i = threadIdx.x + k * nthr;
+    if (i < D.aux_floats) aux[i] = va[k];
+  }
+#pragma unroll
+  for (int k = 0; k < B; ++k) {
+    const int i = threadIdx.x + k * nthr;
+    if (i < n) spp[i] = vp[k];
+  }
+  // (larger shapes: the remaining elements, one at a time)
+  for (int i = threadIdx.x + B * nthr; i < D.aux_floats; i += nthr) aux[i] = ga[i];
+  for (int i = threadIdx.x + B * nthr; i < n; i += nthr) {
+    spp[i] = c < D.Dm ? gpp[t * D.Dm + c] : 0.f;
+    t += dt; c += dc;
+    if (c >= pst) { c -= pst; ++t; }
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the LDS-DMA pieces have landed
+  __syncthreads();
 }
 
 template <int NL>
@@ -379,6 +505,24 @@ DLAP_DEV void tb_issue_kw(const DLAP_GLOBAL uint32_t* gbase, int tile, int ntile
 #pragma unroll
   for (int j = 0; j < NL; ++j)
     kw[j] = (gbase && tile < ntiles) ? *at32(gbase, (uint32_t)((tile * NL + j) * 64 + lane)) : 0xFFFFFFFFu;
+}
+
+// Sum over the 16 lanes of a row in the order of the xor butterfly v += v[l ^ 1], [l ^ 2], [l ^ 4],
+// [l ^ 8], by DPP moves instead of four dependent LDS permutes per value (sixteen values per wave:
+// 64 serial LDS round trips in the epilogue). Same bits: an fp32 add is commutative, so after the
+// levels 1 and 2 the four lanes of a quad hold one value, and after level 4 the eight of a half row;
+// row_half_mirror (lane 7 - i of the eight) and row_mirror (lane 15 - i) therefore deliver exactly
+// what lanes l ^ 4 and l ^ 8 hold.
+template <int CTRL>
+DLAP_DEV float dpp_row(float x) {
+  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, 0xF, 0xF, false));
+}
+DLAP_DEV float row16_sum(float v) {
+  v += dpp_row<0xB1>(v);    // quad_perm [1, 0, 3, 2]
+  v += dpp_row<0x4E>(v);    // quad_perm [2, 3, 0, 1]
+  v += dpp_row<0x141>(v);   // row_half_mirror
+  v += dpp_row<0x140>(v);   // row_mirror
+  return v;
 }
 
 // Fixed-order workgroup combine of the four waves' partials and the slab store, one weight tile
@@ -429,9 +573,7 @@ DLAP_DEV void tb_reduce_store(const MlpJob& J, char* smem, int slab_stride, TbSt
     for (int r = 0; r < 4; ++r) {
       const int o = 16 * u + 4 * q + r;
       if (n < NL) ex[64 * n + o] = S.gb[u][r];
-      float v = S.gwo[u][r];
-      v += __shfl_xor(v, 1, 64); v += __shfl_xor(v, 2, 64);
-      v += __shfl_xor(v, 4, 64); v += __shfl_xor(v, 8, 64);
+      const float v = row16_sum(S.gwo[u][r]);
       if (n == 0) ex[64 * DLAP_MAXL + o] = v;
     }
   const float bo = wave_sum(S.gbo);
@@ -459,16 +601,6 @@ __global__ __launch_bounds__(256, 1) void k_tbwd_sdf(const MlpJob* __restrict__ 
   const int stride = J.nslab * 4;
   const int t0 = blockIdx.x * 4 + wave;
   TbState<NL> S;
-#pragma unroll
-  for (int j = 0; j < NL; ++j)
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-#pragma unroll
-      for (int v = 0; v < 4; ++v) S.dW[j][u][v] = zero4();
-#pragma unroll
-  for (int u = 0; u < 4; ++u) { S.gb[u] = zero4(); S.gwo[u] = zero4(); }
-  S.gbo = 0.f;
-  // prologue: the first two tiles' loads and the step counter in flight with the weight staging
   // prologue: ONE memory round trip -- the step counter, the first two tiles' loads and their keep
   // words of both parity halves (the step's half is not known before the counter arrives) are all
   // in flight with the weight staging, whose drain waits for every one of them; nothing uses the
@@ -482,7 +614,7 @@ __global__ __launch_bounds__(256, 1) void k_tbwd_sdf(const MlpJob* __restrict__ 
     if constexpr (ZIN) issue_ztile<1, true>(J, D, t, in, true, false);
     else issue_tile<P, 2, true>(J, t, in);
   };
-  TI s0, s1, s2;
+  TI s0, s1;
   uint32_t k0[NL], k1[NL], k2[NL];
   if (t0 < ntiles) issue(t0, s0);
   if (t0 + stride < ntiles) issue(t0 + stride, s1);
@@ -494,7 +626,33 @@ __global__ __launch_bounds__(256, 1) void k_tbwd_sdf(const MlpJob* __restrict__ 
   tb_issue_kw<NL>(gb0, t0 + stride, ntiles, k1);
   tb_issue_kw<NL>(gb1, t0, ntiles, a0);
   tb_issue_kw<NL>(gb1, t0 + stride, ntiles, a1);
-  stage_weights<P>(J, D, lds, aux, spp);
+  // (the sums are zeroed under the staging loads: the empty asm pins each zero where it stands --
+  // the compiler otherwise sinks all of them behind the staging barrier, in front of the first tile)
+  // (four layers: the registers for that are not there -- the shared staging, the sums zeroed where
+  // the compiler puts them)
+  auto zero_sums = [&]() __attribute__((always_inline)) {
+#pragma unroll
+    for (int j = 0; j < NL; ++j)
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+          S.dW[j][u][v] = zero4();
+          if constexpr (NL < 4) asm volatile("" : "+a"(S.dW[j][u][v]));
+        }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      S.gb[u] = zero4(); S.gwo[u] = zero4();
+      if constexpr (NL < 4) asm volatile("" : "+a"(S.gb[u]));
+    }
+    S.gbo = 0.f;
+  };
+  if constexpr (NL < 4) {
+    tb_stage(J, D, lds, aux, spp, zero_sums);
+  } else {
+    zero_sums();
+    stage_weights<P>(J, D, lds, aux, spp);
+  }
   asm volatile("" : "+v"(stp_raw));         // (its wave-uniform copy is taken here, not at the load)
   const uint32_t stp = J.step ? stp_raw : 0u;
   const DLAP_GLOBAL uint32_t* gbase = (stp & 1u) ? gb1 : gb0;
@@ -504,15 +662,20 @@ __global__ __launch_bounds__(256, 1) void k_tbwd_sdf(const MlpJob* __restrict__ 
   }
   const TbW<NL, kTbRes<NL>> W(lds, D);
   if (tsb) g_tb_ts[tso + 1] = wall_clock64();
-  // tile loop: the tile two ahead is issued, then the current one runs; the slots rotate by register
-  // copies (unrolling the loop by the three slots instead lets the compiler interleave the bodies,
-  // which spills)
+  // tile loop over two slots: a tile's loads are consumed at its very start (tb_tile's `consumed`
+  // point: the panel fragments are in the image and in xf, dL/dw in two scalars), so there slot 1
+  // moves down into the freed slot 0 -- one copy per tile; its loads were issued a whole tile ago --
+  // and the tile two ahead is issued into slot 1. (Three slots rotated at the end of the iteration
+  // copied twice as much, held 22 more registers through the tile, and the copy of the slot loaded
+  // in that same iteration waited for it just as this one does. Unrolling by the slots instead
+  // spills: 424 bytes of scratch at two layers, with an exit test and a scheduling barrier
+  // between the bodies.)
   for (int t = t0; t < ntiles; t += stride) {
-    if (t + 2 * stride < ntiles) issue(t + 2 * stride, s2);
     tb_issue_kw<NL>(gbase, t + 2 * stride, ntiles, k2);
-    tb_tile<NL, ZIN>(J, D, W, aux, spp, img, im, t, s0, k0, S);
-    s0 = s1;
-    s1 = s2;
+    tb_tile<NL, ZIN>(J, D, W, aux, spp, img, im, t, s0, k0, S, [&] {
+      s0 = s1;
+      if (t + 2 * stride < ntiles) issue(t + 2 * stride, s1);
+    });
 #pragma unroll
     for (int l = 0; l < NL; ++l) { k0[l] = k1[l]; k1[l] = k2[l]; }
   }
