@@ -36,6 +36,7 @@
 #include <chrono>
 
 #include "engine_plan.h"
+#include "knock.h"
 #include "layout.h"
 #include "loss.h"
 #include "macro_sens.h"
@@ -1333,6 +1334,108 @@ class Engine {
     py::dict d;
     d["values"] = vals; d["rows"] = (long long)rows; d["gpu_ms"] = ms; d["tiles_per_wave"] = plan.tiles_per_wave;
     d["period_split"] = plan.period_split;
+    return d;
+  }
+  // Characteristic knock-outs of split s (k_knock.hip, definition in knock.h): the members' and the
+  // ensemble's per-period sums with the columns of each scenario replaced by `base` [F].
+  // masks: uint32 [n_scen][ceil(F / 32)], bit c % 32 of word c / 32 = column c is replaced (an
+  // all-zero row is the baseline). w_out: a dense device buffer [n_scen][T][N] fp32 or 0: the
+  // ensemble weights e / EA are written at the valid (t, i) on the engine stream, every other
+  // element is left as it is. raw_out: a device buffer [n_scen][G][R] fp32 or 0: the raw tower
+  // outputs of every scenario and member (it then serves as the scratch, whatever its size).
+  // raw_in: a device buffer [n_scen][G][R] fp32 or 0: raw weights to reduce in place of the tower
+  // pass (masks and base are then checked and not used).
+  // The scenarios are processed in chunks of at most KNOCK_MAX_CHUNK whose raw-weight scratch
+  // [chunk][G][R] fp32 stays under max_scratch_bytes (0: KNOCK_DEFAULT_SCRATCH, 256 MiB; never
+  // less than one scenario); no output bit depends on the chunking. refresh as for
+  // input_sensitivity. Returns fp64 n, sum_r, sum_rr [T]; EA, E2, ER [K][T]; S1, SA, SR
+  // [K][G][T]; rows, chunks, and fwd_ms / reduce_ms (GPU time of the two kernels over all chunks).
+  bool knock_ok(int s) const {
+    return s >= 0 && s <= 2 && splits_[s].set && !xs_on_ && knock_supported(md_.md, md_.KS1, splits_[s].T);
+  }
+  py::dict knockout(int s, py::array_t<uint32_t, py::array::c_style | py::array::forcecast> masks, int n_scen,
+                    std::vector<float> base, uintptr_t w_out = 0, bool refresh = true, size_t max_scratch_bytes = 0,
+                    uintptr_t raw_out = 0, uintptr_t raw_in = 0) {
+    check_split(s, "knockout", kSplitIndex, true);
+    if (raw_in && raw_out) throw std::invalid_argument("knockout: raw_in and raw_out exclude each other");
+    const int F = md_.F, W = (F + 31) / 32, K = n_scen;
+    if (K < 1) throw std::invalid_argument("knockout: no scenarios");
+    if (masks.size() != (py::ssize_t)K * W) throw std::invalid_argument("knockout: masks must be [n_scen][ceil(F / 32)]");
+    if ((int)base.size() != F) throw std::invalid_argument("knockout: base must have F entries");
+    const uint32_t* hm = masks.data();
+    for (int k = 0; k < K; ++k)
+      for (int c = F; c < 32 * W; ++c)
+        if ((hm[(size_t)k * W + c / 32] >> (c % 32)) & 1u) throw std::invalid_argument("knockout: column outside [0, F)");
+    if (xs_on_) throw std::invalid_argument("knockout: a single rank only (the engine is sharded)");
+    check_split(s, "knockout", kSplitSet | kSplitPeriods, true);
+    ensure_jobs();
+    const SplitDev& D = splits_[s];
+    if (!knock_supported(md_.md, md_.KS1, D.T))
+      throw std::invalid_argument("knockout: not available for this shape (wide layer-0 path, or the fragments and "
+                                  "per-period inputs exceed the LDS budget)");
+    const int T = D.T, G = G_;
+    auto pn = filled<double>({T}, 0.0), psr = filled<double>({T}, 0.0), psrr = filled<double>({T}, 0.0);
+    py::array_t<double> ens[3], mem[3];
+    for (auto& a : ens) a = filled<double>({K, T}, 0.0);
+    for (auto& a : mem) a = filled<double>({K, G, T}, 0.0);
+    float fwd_ms = 0.f, red_ms = 0.f;
+    int chunks = 0;
+    if (D.R > 0) {                            // (an empty split launches nothing and reads nothing)
+      if (refresh && !raw_in) fwd_only(s, false, false, false);
+      // buffers of this call (an analysis pass, not a step of an epoch), released on return
+      if (raw_in) raw_out = raw_in;
+      const size_t per_scen = (size_t)G * D.R * sizeof(float);
+      const size_t lim = max_scratch_bytes ? max_scratch_bytes : (size_t)KNOCK_DEFAULT_SCRATCH;
+      const int KC = (int)std::min<size_t>(std::min(K, KNOCK_MAX_CHUNK), std::max<size_t>(lim / per_scen, 1));
+      const int KS = md_.KP / 32;
+      std::vector<uint32_t> pm((size_t)K * KS, 0u);
+      for (int k = 0; k < K; ++k) std::copy(hm + (size_t)k * W, hm + (size_t)(k + 1) * W, pm.begin() + (size_t)k * KS);
+      std::vector<float> hb((size_t)md_.KP, 0.f);
+      std::copy(base.begin(), base.end(), hb.begin());
+      DevBuf<char> tj;
+      DevBuf<uint32_t> dm;
+      DevBuf<float> dbase, wk;
+      DevBuf<double> dens, dmem, dper;
+      up(dm, pm.data(), pm.size());
+      up(dbase, hb.data(), hb.size());
+      eval_jobs(s, tj);
+      if (!raw_out) wk.alloc((size_t)KC * G * D.R, false);
+      dens.alloc((size_t)3 * KC * T, false); dmem.alloc((size_t)3 * KC * G * T, false); dper.alloc((size_t)3 * T, false);
+      std::vector<double> he((size_t)3 * KC * T), hg((size_t)3 * KC * G * T);
+      for (int k0 = 0; k0 < K; k0 += KC, ++chunks) {
+        const int kc = std::min(KC, K - k0);
+        float* w = raw_out ? reinterpret_cast<float*>(raw_out) + (size_t)k0 * G * D.R : wk.p;
+        KnockArgs A{};
+        A.masks = dm.p + (size_t)k0 * KS; A.base = dbase.p; A.K = kc; A.G = G; A.R = D.R; A.T = T; A.wk = w;
+        KnockReduceArgs B{};
+        B.pv = panel_view(D);
+        B.wk = w; B.K = kc; B.G = G; B.R = D.R; B.normalize_w = md_.normalize_w ? 1 : 0;
+        B.ens = dens.p; B.mem = dmem.p; B.per = k0 == 0 ? dper.p : nullptr;
+        B.dense = w_out ? reinterpret_cast<float*>(w_out) + (size_t)k0 * T * D.N : nullptr;
+        GpuTimer tm(st_, 3);
+        tm.mark();
+        if (!raw_in) launch_knock_fwd(as<MlpJob>(tj), A, md_.md, md_.KS1, st_);
+        tm.mark();
+        launch_knock_reduce(B, st_);
+        tm.mark();
+        sync();
+        fwd_ms += tm.ms(0); red_ms += tm.ms(1);
+        fetch(he.data(), dens.p, (size_t)3 * kc * T);
+        fetch(hg.data(), dmem.p, (size_t)3 * kc * G * T);
+        for (int j = 0; j < 3; ++j) {
+          std::copy_n(he.data() + (size_t)j * kc * T, (size_t)kc * T, ens[j].mutable_data() + (size_t)k0 * T);
+          std::copy_n(hg.data() + (size_t)j * kc * G * T, (size_t)kc * G * T, mem[j].mutable_data() + (size_t)k0 * G * T);
+        }
+      }
+      fetch(pn, dper.p);
+      fetch(psr, dper.p + T);
+      fetch(psrr, dper.p + 2 * (size_t)T);
+    }
+    py::dict d;
+    d["n"] = pn; d["sum_r"] = psr; d["sum_rr"] = psrr;
+    d["EA"] = ens[0]; d["E2"] = ens[1]; d["ER"] = ens[2];
+    d["S1"] = mem[0]; d["SA"] = mem[1]; d["SR"] = mem[2];
+    d["rows"] = D.R; d["chunks"] = chunks; d["fwd_ms"] = fwd_ms; d["reduce_ms"] = red_ms;
     return d;
   }
   void train_step(int phase, float lr) {
@@ -3331,6 +3434,10 @@ PYBIND11_MODULE(_dlap_hip, m) {
       .def("weight_surface", &Engine::weight_surface, py::arg("s"), py::arg("scale"), py::arg("grid"), py::arg("base"),
            py::arg("items"), py::arg("refresh") = true)
       .def("weight_surface_supported", [](Engine& e, int s) { return e.wsurf_ok(s); }, py::arg("s") = 0)
+      .def("knockout", &Engine::knockout, py::arg("s"), py::arg("masks"), py::arg("n_scen"), py::arg("base"),
+           py::arg("w_out") = 0, py::arg("refresh") = true, py::arg("max_scratch_bytes") = 0, py::arg("raw_out") = 0,
+           py::arg("raw_in") = 0)
+      .def("knockout_supported", [](Engine& e, int s) { return e.knock_ok(s); }, py::arg("s") = 0)
       .def("train_step", &Engine::train_step)
       .def("backward_only", &Engine::backward_only, py::arg("phase"), py::arg("wait") = true)
       .def("set_stream", &Engine::set_stream, py::arg("stream"), py::arg("external") = true)

@@ -1,6 +1,6 @@
 // The resident panel of one split as the panel-only kernels see it (k_qsort.hip, k_qsort2.hip,
-// k_linport.hip, k_xgram.hip): the compacted rows the engine keeps on the device, no model, job
-// table or graph. Their argument structs embed it as the first member `pv`; the engine fills it in
+// k_linport.hip, k_xgram.hip; k_knock.hip's reduction reads its panel side through it): the
+// compacted rows the engine keeps on the device, no model, job table or graph. Their argument structs embed it as the first member `pv`; the engine fills it in
 // one place (Engine::panel_view). A pass reads the fields it needs (k_xgram reads no rowti or N).
 #pragma once
 #include "common.h"

@@ -98,7 +98,9 @@ def evaluate_ensemble(checkpoint_dirs: Sequence[str], data_dir: str, device: str
                       benchmarks_out: str = None, benchmark_ffn: bool = False, beta_network: bool = False,
                       prediction_epochs: int = 64, prediction_lr: float = None, prediction_seeds=(0,),
                       prediction_out: str = None, benchmark_ipca: bool = False, ipca_factors=(1, 2, 3, 4, 5, 6),
-                      ipca_intercept: bool = True, fama_macbeth: bool = False, fm_out: str = None) -> Dict:
+                      ipca_intercept: bool = True, fama_macbeth: bool = False, fm_out: str = None,
+                      knockout: bool = False, knockout_split: str = "test", knockout_groups=None,
+                      knockout_base="zero", knockout_xs_r2: bool = False, knockout_out: str = None) -> Dict:
     """Reference output and return value; ``paper=True`` (CLI ``--paper_metrics``) adds the
     paper's EV / XS-R² / turnover / max 1-month loss of the ensemble's SDF factor per split;
     ``importance=True`` (CLI ``--variable_importance``) adds the sensitivity ranking of the
@@ -139,7 +141,13 @@ def evaluate_ensemble(checkpoint_dirs: Sequence[str], data_dir: str, device: str
     ``fama_macbeth=True`` (CLI ``--fama_macbeth``) prints the Fama-MacBeth slope table of ``sort_split``
     (``analysis.ipca.fama_macbeth``), under the key ``fama_macbeth``, and writes it to ``fm_out`` (JSON)
     when given. Both use the per-period characteristic Gram: ``Engine.characteristic_gram`` with
-    ``device="cuda"``, numpy otherwise."""
+    ``device="cuda"``, numpy otherwise;
+    ``knockout=True`` (CLI ``--knockout``) adds the characteristic knock-outs of ``knockout_split``
+    (``analysis.knockout.knockout_importance``: the baseline, one scenario per characteristic and one per
+    entry of ``knockout_groups``, a dict or the CLI's JSON file of name -> columns or names; ``knockout_base``:
+    ``zero``, ``median`` or an [F] array; ``knockout_xs_r2`` adds XS-R²) under the key ``knockout``, prints
+    one table (scenario, Sharpe, d Sharpe, EV, d EV) and writes the report to ``knockout_out`` (JSON) when
+    given."""
     say = print if verbose else (lambda *a, **k: None)
     bar = "=" * 70
     say(bar); say(f"ENSEMBLE EVALUATION ({len(checkpoint_dirs)} models, averaged weights)"); say(bar); say()
@@ -363,6 +371,24 @@ def evaluate_ensemble(checkpoint_dirs: Sequence[str], data_dir: str, device: str
             with open(structure_out, "w") as fh:
                 json.dump(wst.to_json(res_ws), fh, indent=1)
             say(f"  Saved: {structure_out}"); say()
+    if knockout:
+        from . import knockout as ko
+        if knockout_split not in SPLITS:
+            raise ValueError(f"knockout_split must be one of {SPLITS}")
+        ds = datasets[SPLITS.index(knockout_split)]
+        groups = ko.load_groups(knockout_groups) if isinstance(knockout_groups, str) else knockout_groups
+        rep = ko.knockout_importance(models, batches[knockout_split], groups=groups, base=knockout_base,
+                                     xs_r2=knockout_xs_r2, device=device, names=getattr(ds, "variable_names", None))
+        out["knockout"] = rep
+        say(bar); say(f"CHARACTERISTIC KNOCK-OUTS ({knockout_split} split, ensemble SDF, {rep['path']} path)")
+        say(bar); say()
+        for line in ko.format_knockout(rep):
+            say(line)
+        say()
+        if knockout_out:
+            with open(knockout_out, "w") as fh:
+                json.dump(ko.to_json(rep), fh, indent=1)
+            say(f"  Saved: {knockout_out}"); say()
     return out
 
 
@@ -417,6 +443,14 @@ def _parser():
     p.add_argument("--fama_macbeth", action="store_true",
                    help="also print the Fama-MacBeth slope table of --sort_split")
     p.add_argument("--fm_out", type=str, default=None, help="write the Fama-MacBeth table to FILE.json")
+    p.add_argument("--knockout", action="store_true",
+                   help="also print what the ensemble SDF loses without each characteristic (and each group)")
+    p.add_argument("--knockout_split", type=str, default="test", choices=SPLITS)
+    p.add_argument("--knockout_groups", type=str, default=None,
+                   help="FILE.json: {group name: [columns or characteristic names]}, one scenario per group")
+    p.add_argument("--knockout_base", type=str, default="zero", choices=("zero", "median"))
+    p.add_argument("--knockout_xs_r2", action="store_true", help="with --knockout: also XS-R2 per scenario")
+    p.add_argument("--knockout_out", type=str, default=None, help="write the knock-out report to FILE.json")
     return p
 
 
@@ -448,6 +482,9 @@ def _extra_kwargs(a) -> Dict:
         kw.update(benchmark_ipca=True, ipca_factors=tuple(a.ipca_factors), ipca_intercept=not a.ipca_no_intercept)
     if a.fama_macbeth:
         kw.update(fama_macbeth=True, fm_out=a.fm_out, sort_split=a.sort_split, ipca_intercept=not a.ipca_no_intercept)
+    if a.knockout:
+        kw.update(knockout=True, knockout_split=a.knockout_split, knockout_groups=a.knockout_groups,
+                  knockout_base=a.knockout_base, knockout_xs_r2=a.knockout_xs_r2, knockout_out=a.knockout_out)
     return kw
 
 
