@@ -1438,6 +1438,183 @@ class Engine {
     d["rows"] = D.R; d["chunks"] = chunks; d["fwd_ms"] = fwd_ms; d["reduce_ms"] = red_ms;
     return d;
   }
+  // Macro knock-outs of split s (definition in knock.h): Engine.knockout with, per scenario, also
+  // a set of macro series held at macro_base [M] over the whole split. macro_masks: uint32
+  // [n_scen][ceil(M / 32)], bit j % 32 of word j / 32 = series j is replaced. masks, base, w_out,
+  // raw_out and refresh as for knockout. Per chunk of scenarios: k_knock_macro_fill writes the
+  // altered series of the scenarios with a non-empty macro set; with an LSTM one launch_prologue
+  // over (those scenarios) x G jobs -- the split's evaluation jobs with the copy as macro input and
+  // out / xg / xin in scratch of this call -- gives one [T][Dm] table per (scenario, member), without
+  // an LSTM the copies are the tables; k_knock_fwd_pp, then k_knock_reduce. A scenario with an empty
+  // macro set runs no recurrence and reads the split's own table (refresh). max_scratch_bytes (0:
+  // KNOCK_DEFAULT_SCRATCH) bounds everything allocated per chunk -- raw weights, copies, LSTM
+  // scratch and tables -- and never allows less than one scenario; no output bit depends on the
+  // chunking. Returns what knockout returns, plus lstm_ms (fill + prologue) and lstm_jobs.
+  bool knock_macro_ok(int s) const {
+    return knock_ok(s) && md_.M >= 1 && knock_pp_supported(md_.md, md_.KS1, splits_[s].T);
+  }
+  py::dict knockout_macro(int s, py::array_t<uint32_t, py::array::c_style | py::array::forcecast> masks,
+                          py::array_t<uint32_t, py::array::c_style | py::array::forcecast> macro_masks, int n_scen,
+                          std::vector<float> base, std::vector<float> macro_base, uintptr_t w_out = 0,
+                          bool refresh = true, size_t max_scratch_bytes = 0, uintptr_t raw_out = 0) {
+    check_split(s, "knockout_macro", kSplitIndex, true);
+    const int F = md_.F, W = (F + 31) / 32, M = md_.M, MW = (M + 31) / 32, K = n_scen;
+    if (K < 1) throw std::invalid_argument("knockout_macro: no scenarios");
+    if (M < 1) throw std::invalid_argument("knockout_macro: the models have no macro input");
+    if (masks.size() != (py::ssize_t)K * W) throw std::invalid_argument("knockout_macro: masks must be [n_scen][ceil(F / 32)]");
+    if (macro_masks.size() != (py::ssize_t)K * MW)
+      throw std::invalid_argument("knockout_macro: macro_masks must be [n_scen][ceil(M / 32)]");
+    if ((int)base.size() != F) throw std::invalid_argument("knockout_macro: base must have F entries");
+    if ((int)macro_base.size() != M) throw std::invalid_argument("knockout_macro: macro_base must have M entries");
+    const uint32_t* hm = masks.data();
+    const uint32_t* hq = macro_masks.data();
+    for (int k = 0; k < K; ++k) {
+      for (int c = F; c < 32 * W; ++c)
+        if ((hm[(size_t)k * W + c / 32] >> (c % 32)) & 1u) throw std::invalid_argument("knockout_macro: column outside [0, F)");
+      for (int j = M; j < 32 * MW; ++j)
+        if ((hq[(size_t)k * MW + j / 32] >> (j % 32)) & 1u) throw std::invalid_argument("knockout_macro: macro series outside [0, M)");
+    }
+    if (xs_on_) throw std::invalid_argument("knockout_macro: a single rank only (the engine is sharded)");
+    check_split(s, "knockout_macro", kSplitSet | kSplitPeriods, true);
+    ensure_jobs();
+    const SplitDev& D = splits_[s];
+    if (!knock_pp_supported(md_.md, md_.KS1, D.T))
+      throw std::invalid_argument("knockout_macro: not available for this shape (wide layer-0 path, or the fragments and "
+                                  "per-period inputs exceed the LDS budget)");
+    const int T = D.T, G = G_, Dm = md_.Dm, H = md_.H;
+    const bool lstm = md_.nrnn > 0;
+    auto pn = filled<double>({T}, 0.0), psr = filled<double>({T}, 0.0), psrr = filled<double>({T}, 0.0);
+    py::array_t<double> ens[3], mem[3];
+    for (auto& a : ens) a = filled<double>({K, T}, 0.0);
+    for (auto& a : mem) a = filled<double>({K, G, T}, 0.0);
+    float fwd_ms = 0.f, red_ms = 0.f, lstm_ms = 0.f;
+    int chunks = 0;
+    long long lstm_jobs = 0;
+    if (D.R > 0) {                            // (an empty split launches nothing and reads nothing)
+      if (refresh) fwd_only(s, false, false, false);
+      // a scenario's macro set matters only where the tower reads per-period inputs
+      std::vector<char> hasq((size_t)K, 0);
+      if (Dm > 0)
+        for (int k = 0; k < K; ++k)
+          for (int w = 0; w < MW; ++w) hasq[k] |= hq[(size_t)k * MW + w] != 0;
+      // per scenario of a chunk: raw weights [G][R], the copy [T][M], and per member the table
+      // [T][H] and the recurrence's xg [T][4H] and xin [T][H]; the copy is the table without an LSTM
+      const size_t cstride = knock_fill_stride(T, M);
+      const size_t tstride = lstm ? (((size_t)T * 6 * H + 3) & ~(size_t)3) : 0;   // [out | xg | xin] of one job
+      const size_t per_scen = (raw_out ? 0 : (size_t)G * D.R * sizeof(float)) + cstride * sizeof(float) +
+                              (size_t)G * tstride * sizeof(float);
+      const size_t lim = max_scratch_bytes ? max_scratch_bytes : (size_t)KNOCK_DEFAULT_SCRATCH;
+      const int KC = (int)std::min<size_t>(std::min<size_t>(std::min(K, KNOCK_MAX_CHUNK), (size_t)65535 / G),
+                                           std::max<size_t>(lim / std::max<size_t>(per_scen, 1), 1));
+      const int KS = md_.KP / 32;
+      std::vector<uint32_t> pm((size_t)K * KS, 0u);
+      for (int k = 0; k < K; ++k) std::copy(hm + (size_t)k * W, hm + (size_t)(k + 1) * W, pm.begin() + (size_t)k * KS);
+      std::vector<float> hb((size_t)md_.KP, 0.f);
+      std::copy(base.begin(), base.end(), hb.begin());
+      DevBuf<char> tj, trj;
+      DevBuf<uint32_t> dm, dq;
+      DevBuf<float> dbase, dmb, wk, copies, lscr, junk;
+      DevBuf<const float*> dtabs;
+      DevBuf<double> dens, dmem, dper;
+      up(dm, pm.data(), pm.size());
+      up(dbase, hb.data(), hb.size());
+      up(dmb, macro_base.data(), macro_base.size());
+      eval_jobs(s, tj);
+      // the split's evaluation recurrences as fwd_only launches them, less what an analysis pass
+      // must not touch: no saved gates, no moment bias table, no progress counter (k_proj zeroes
+      // the counter of a job that carries one)
+      std::vector<RnnJob> rj0;
+      if (lstm)
+        for (int g = 0; g < G; ++g) {
+          RnnJob r = rnn_job(g, s, false, 0);
+          r.train = 0; r.sg = nullptr; r.sc = nullptr; r.sh = nullptr; r.abias = nullptr; r.prog = nullptr;
+          rj0.push_back(r);
+        }
+      // k_proj's last 16-column tile stores the columns from 4H on to the job's bias table: where
+      // 4H is no multiple of 16 the jobs share one table of this call that nothing reads
+      if (lstm && (4 * H) % 16 != 0) {
+        junk.alloc((size_t)T * 64, false);
+        for (RnnJob& r : rj0) r.abias = junk.p;
+      }
+      if (!raw_out) wk.alloc((size_t)KC * G * D.R, false);
+      if (Dm > 0) { copies.alloc((size_t)KC * cstride, false); dq.alloc((size_t)KC * MW, false); }
+      if (lstm) lscr.alloc((size_t)KC * G * tstride, false);
+      dtabs.alloc((size_t)KC * G, false);
+      dens.alloc((size_t)3 * KC * T, false); dmem.alloc((size_t)3 * KC * G * T, false); dper.alloc((size_t)3 * T, false);
+      std::vector<double> he((size_t)3 * KC * T), hg((size_t)3 * KC * G * T);
+      std::vector<const float*> htabs((size_t)KC * G);
+      std::vector<uint32_t> hqc((size_t)KC * MW);
+      std::vector<RnnJob> rj;
+      for (int k0 = 0; k0 < K; k0 += KC, ++chunks) {
+        const int kc = std::min(KC, K - k0);
+        // the chunk's scenarios with a macro set, in order: copy u, jobs u * G + g
+        int U = 0;
+        rj.clear();
+        for (int k = 0; k < kc; ++k) {
+          if (!hasq[k0 + k]) {
+            for (int g = 0; g < G; ++g) htabs[(size_t)k * G + g] = pp_ptr(g, s);
+            continue;
+          }
+          std::copy(hq + (size_t)(k0 + k) * MW, hq + (size_t)(k0 + k + 1) * MW, hqc.begin() + (size_t)U * MW);
+          const float* cp = copies.p + (size_t)U * cstride;
+          for (int g = 0; g < G; ++g) {
+            if (!lstm) { htabs[(size_t)k * G + g] = cp; continue; }
+            float* o = lscr.p + ((size_t)U * G + g) * tstride;
+            RnnJob r = rj0[g];
+            r.macro = cp; r.out = o; r.xg = o + (size_t)T * H; r.xin = o + (size_t)T * 5 * H;
+            rj.push_back(r);
+            htabs[(size_t)k * G + g] = o;
+          }
+          ++U;
+        }
+        HIP_LEGACY(hipMemcpy(dtabs.p, htabs.data(), (size_t)kc * G * sizeof(const float*), hipMemcpyHostToDevice));
+        if (U > 0) HIP_LEGACY(hipMemcpy(dq.p, hqc.data(), (size_t)U * MW * sizeof(uint32_t), hipMemcpyHostToDevice));
+        if (!rj.empty()) upload(trj, rj);
+        float* w = raw_out ? reinterpret_cast<float*>(raw_out) + (size_t)k0 * G * D.R : wk.p;
+        KnockPpArgs A{};
+        A.a.masks = dm.p + (size_t)k0 * KS; A.a.base = dbase.p; A.a.K = kc; A.a.G = G; A.a.R = D.R; A.a.T = T; A.a.wk = w;
+        A.tabs = dtabs.p;
+        KnockReduceArgs B{};
+        B.pv = panel_view(D);
+        B.wk = w; B.K = kc; B.G = G; B.R = D.R; B.normalize_w = md_.normalize_w ? 1 : 0;
+        B.ens = dens.p; B.mem = dmem.p; B.per = k0 == 0 ? dper.p : nullptr;
+        B.dense = w_out ? reinterpret_cast<float*>(w_out) + (size_t)k0 * T * D.N : nullptr;
+        GpuTimer tm(st_, 4);
+        tm.mark();
+        if (U > 0) {
+          KnockFillArgs Fa{};
+          Fa.macro = D.macro.p; Fa.masks = dq.p; Fa.base = dmb.p; Fa.out = copies.p; Fa.stride = cstride;
+          Fa.U = U; Fa.T = T; Fa.M = M;
+          launch_knock_macro_fill(Fa, st_);
+          if (lstm) launch_prologue(as<RnnJob>(trj), U * G, T, dd(), md_, st_, false, true);
+          lstm_jobs += lstm ? (long long)U * G : 0;
+        }
+        tm.mark();
+        launch_knock_fwd_pp(as<MlpJob>(tj), A, md_.md, md_.KS1, st_);
+        tm.mark();
+        launch_knock_reduce(B, st_);
+        tm.mark();
+        sync();
+        lstm_ms += tm.ms(0); fwd_ms += tm.ms(1); red_ms += tm.ms(2);
+        fetch(he.data(), dens.p, (size_t)3 * kc * T);
+        fetch(hg.data(), dmem.p, (size_t)3 * kc * G * T);
+        for (int j = 0; j < 3; ++j) {
+          std::copy_n(he.data() + (size_t)j * kc * T, (size_t)kc * T, ens[j].mutable_data() + (size_t)k0 * T);
+          std::copy_n(hg.data() + (size_t)j * kc * G * T, (size_t)kc * G * T, mem[j].mutable_data() + (size_t)k0 * G * T);
+        }
+      }
+      fetch(pn, dper.p);
+      fetch(psr, dper.p + T);
+      fetch(psrr, dper.p + 2 * (size_t)T);
+    }
+    py::dict d;
+    d["n"] = pn; d["sum_r"] = psr; d["sum_rr"] = psrr;
+    d["EA"] = ens[0]; d["E2"] = ens[1]; d["ER"] = ens[2];
+    d["S1"] = mem[0]; d["SA"] = mem[1]; d["SR"] = mem[2];
+    d["rows"] = D.R; d["chunks"] = chunks; d["fwd_ms"] = fwd_ms; d["reduce_ms"] = red_ms;
+    d["lstm_ms"] = lstm_ms; d["lstm_jobs"] = lstm_jobs;
+    return d;
+  }
   void train_step(int phase, float lr) {
     check_phase(phase);
     ensure_jobs();
@@ -3438,6 +3615,10 @@ PYBIND11_MODULE(_dlap_hip, m) {
            py::arg("w_out") = 0, py::arg("refresh") = true, py::arg("max_scratch_bytes") = 0, py::arg("raw_out") = 0,
            py::arg("raw_in") = 0)
       .def("knockout_supported", [](Engine& e, int s) { return e.knock_ok(s); }, py::arg("s") = 0)
+      .def("knockout_macro", &Engine::knockout_macro, py::arg("s"), py::arg("masks"), py::arg("macro_masks"),
+           py::arg("n_scen"), py::arg("base"), py::arg("macro_base"), py::arg("w_out") = 0, py::arg("refresh") = true,
+           py::arg("max_scratch_bytes") = 0, py::arg("raw_out") = 0)
+      .def("knockout_macro_supported", [](Engine& e, int s) { return e.knock_macro_ok(s); }, py::arg("s") = 0)
       .def("train_step", &Engine::train_step)
       .def("backward_only", &Engine::backward_only, py::arg("phase"), py::arg("wait") = true)
       .def("set_stream", &Engine::set_stream, py::arg("stream"), py::arg("external") = true)

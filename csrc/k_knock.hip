@@ -25,6 +25,11 @@
 //                    four waves in order through LDS. A sum depends on wk[k] of its own scenario
 //                    (and member) and the panel only: not on the chunking, the scenario's position
 //                    or the other members.
+//   k_knock_macro_fill, k_knock_fwd_pp   macro knock-outs (knock.h): the altered series of a
+//                    chunk's scenarios, and the tower pass of k_knock_fwd with one per-period
+//                    table per (scenario, member) inserted per scenario (described at the kernel).
+//                    The same ownership, stores and bits as k_knock_fwd where the table is the
+//                    split's own.
 // LDS of k_knock_fwd: [blob | aux | pp [T][ppst]] (tower_dev.h), then the masks of a full chunk.
 #include <algorithm>
 #include "common.h"
@@ -120,6 +125,190 @@ void k_knock_fwd(const MlpJob* __restrict__ jobs, KnockArgs A, MlpDims D) {
         }
       }
     }
+  }
+}
+
+// ---- macro knock-outs: one per-period table per (scenario, member) ----------------------------
+// LDS of k_knock_fwd_pp: [blob | aux] (no per-period inputs), the masks of a full chunk, then the
+// current member's table pointers of a full chunk.
+MlpDims knock_pp_dims(const MlpDims& D0) {
+  MlpDims D = D0;
+  D.pp_lds_floats = 0;
+  return D;
+}
+__host__ __device__ inline size_t knock_tab_base(const MlpDims& D, int KS1) { return (knock_lds_bytes(D, KS1) + 15) & ~(size_t)15; }
+__host__ __device__ inline size_t knock_pp_lds_bytes(const MlpDims& D, int KS1) {
+  return knock_tab_base(D, KS1) + (size_t)KNOCK_MAX_CHUNK * sizeof(const float*);
+}
+
+// k_knock_fwd with the [ppc, ppc + Dm) columns of the fragments taken per scenario from the fp32
+// table tabs[k][g] ([T][Dm]: the LSTM output, or the macro series themselves, of the scenario's
+// altered series). The tile is loaded once per member without the insertion (finish_tile<INS =
+// false>); per scenario the characteristic mask is applied as in k_knock_fwd and the lane groups
+// whose 8 columns fall into the per-period range take pp[t(row)][c0 .. c0 + 7] with the conversion
+// of the forward's staged path (P::pack of the fp32 values, zero beyond Dm), replacing the whole
+// fragment where c0 >= 0 and the row is inside R, as finish_tile does.
+// The rows are read from global memory (the tables are small and stay in L2; 16-byte loads where
+// Dm is a multiple of 4, else 4-byte loads with clamped columns), and the next scenario's rows are
+// in flight while the current scenario's tower runs: they are issued right after the current rows
+// were packed and waited for at the top of the next iteration. This is the variant that was built
+// and measured (profiles/macro_knockout_timing.txt); staging sub-chunks of tables in LDS was not:
+// with K * G tables of T * Dm floats each, a sub-chunk would have to be restaged (a barrier and a
+// round trip) every few scenarios, while the loads here overlap the MFMAs of a whole tower.
+// NS: the trailing k-steps of the row that can hold per-period columns (k-step s holds some iff
+// 32 s + 32 > ppc), so only their rows take registers. PRE: the prefetch above; without it (the
+// builds the launcher picks where the 8 * 2 * NS fp32 values in flight across a tower would not
+// fit the register budget) the rows are loaded where they are packed.
+// VEC: Dm is a multiple of 4, so the rows of a table are 16-byte aligned (the tables are, and a
+// lane's first column is a multiple of 8): two 16-byte loads per fragment, else eight 4-byte loads.
+template <class P, int KS1, int NS, bool PRE, bool VEC>
+__global__ __launch_bounds__(256, P::kF32 ? 1 : 2)
+void k_knock_fwd_pp(const MlpJob* __restrict__ jobs, KnockPpArgs B, MlpDims D) {
+  using Frag = typename P::Frag;
+  static_assert(NS >= 1 && NS <= KS1, "per-period k-steps");
+  const KnockArgs& A = B.a;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  Frag* lds = reinterpret_cast<Frag*>(smem);
+  float* aux = aux_lds_ptr(smem, D);
+  uint32_t* smask = reinterpret_cast<uint32_t*>(smem + knock_mask_base(D));      // [K][KS1]
+  const float** stab = reinterpret_cast<const float**>(smem + knock_tab_base(D, KS1));   // [K]
+  const int lane = lane_id(), wave = threadIdx.x >> 6, q = lane >> 4, n = lane & 15;
+  const int ntiles = (A.R + 31) >> 5;
+  const int tile0 = blockIdx.x * (4 * kTPW) + wave;           // this wave's tiles: tile0 + 4 k
+  for (int i = threadIdx.x; i < A.K * KS1; i += blockDim.x) smask[i] = gp(A.masks)[i];
+  Frag bf[KS1];
+#pragma unroll
+  for (int s = 0; s < KS1; ++s) {
+    const int c0 = 32 * s + 8 * q;
+    const f32x4 lo = ld4(gp(A.base) + c0), hi = ld4(gp(A.base) + c0 + 4);
+    bf[s] = P::zero();
+#pragma unroll
+    for (int j = 0; j < 8; ++j) P::set(bf[s], j, j < 4 ? lo[j & 3] : hi[j & 3]);
+  }
+  const uint32_t kw[4] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
+  const bool ins = D.Dm > 0;
+  for (int g = 0; g < A.G; ++g) {
+    const MlpJob J = jobs[g];
+    DLAP_ASSERT(J.R == A.R && J.T == A.T);
+    __syncthreads();                                   // every wave is done with the previous model's image
+    if (ins)
+      for (int k = threadIdx.x; k < A.K; k += blockDim.x) stab[k] = gp(B.tabs)[(size_t)k * A.G + g];
+    stage_weights<P>(J, D, lds, aux);                  // (ends with a barrier: masks and pointers are complete too)
+#pragma unroll 1
+    for (int kt = 0; kt < kTPW; ++kt) {
+      const int tile = tile0 + 4 * kt;
+      if (tile >= ntiles) break;                       // wave-uniform; no barrier below
+      TileIn<P, KS1> in;
+      issue_tile<P, KS1, false>(J, tile, in);          // rows clamped to R - 1
+      Frag xf[2][KS1];
+      const RowInfo ri = finish_tile<P, KS1, false>(J, D, tile, in, xf);
+      const bool okr[2] = {ri.dense[0] >= 0, ri.dense[1] >= 0};
+      const int ro[2] = {ri.t[0] * D.Dm, ri.t[1] * D.Dm};       // (clamped rows carry a valid period)
+      // the 8 columns of this lane in k-step s start at pp column 32 s + 8 q - ppc
+      float raw[2][NS][8];
+      // (z: the scenario loop's opaque zero -- the clamped columns and the range predicates are
+      // formed per scenario, not kept in registers across the towers)
+      auto load_frag = [&](const float* tab, int u, int b, int z) {
+        const auto tp = gp(tab);
+        const int c0 = 32 * (KS1 - NS + u) + 8 * q - D.ppc + z;
+        if constexpr (VEC) {
+          const int ca = min(max(c0, 0), D.Dm - 4), cb = min(max(c0 + 4, 0), D.Dm - 4);
+          const f32x4 v0 = ld4(tp + ro[b] + ca);
+          f32x4 v1 = zero4();
+          if (D.Dm > 4) v1 = ld4(tp + ro[b] + cb);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) { raw[b][u][j] = v0[j]; raw[b][u][4 + j] = v1[j]; }
+        } else {
+#pragma unroll
+          for (int j = 0; j < 8; ++j) raw[b][u][j] = tp[ro[b] + min(max(c0 + j, 0), D.Dm - 1)];
+        }
+      };
+      auto load_rows = [&](const float* tab, int z) {
+#pragma unroll
+        for (int u = 0; u < NS; ++u)
+#pragma unroll
+          for (int b = 0; b < 2; ++b) load_frag(tab, u, b, z);
+      };
+      if (PRE && ins) load_rows(stab[0], 0);
+      float* dst = A.wk + (size_t)g * A.R + tile * 32 + n;
+      auto store_w = [&](int k, const float (&w)[2]) {
+        if (q == 0) {
+          float* d = dst + (size_t)k * A.G * A.R;
+          if (tile * 32 + n < A.R) *gp(d) = w[0];
+          if (tile * 32 + 16 + n < A.R) *gp(d + 16) = w[1];
+        }
+      };
+      float wp[2] = {0.f, 0.f};                        // PRE: the previous scenario's weights
+#pragma unroll 1
+      for (int k = 0; k < A.K; ++k) {
+        const int oz = opaque_zero();                  // no weight fragment kept across scenarios
+        const int zc = NS == 1 && VEC ? 0 : oz;        // (one k-step, two loads: columns and predicates stay in registers)
+        const Frag* ldt = lds + oz;
+        const float* auxt = aux + oz;
+        MlpDims Dt = D;
+        Dt.nl_sdf += oz;
+        Frag xk[2][KS1];
+#pragma unroll
+        for (int s = 0; s < KS1; ++s) {
+          const uint32_t m = smask[k * KS1 + s] >> (8 * q);
+#pragma unroll
+          for (int b = 0; b < 2; ++b) {
+            xk[b][s] = xf[b][s];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) xk[b][s][j] = ((m >> j) & 1u) ? bf[s][j] : xf[b][s][j];
+          }
+        }
+        if (ins) {
+#pragma unroll
+          for (int u = 0; u < NS; ++u) {
+            const int s = KS1 - NS + u;
+            const int c0 = 32 * s + 8 * q - D.ppc + zc;
+#pragma unroll
+            for (int b = 0; b < 2; ++b) {
+              if (!PRE) {                              // one fragment's rows at a time, consumed below
+                asm volatile("" ::: "memory");
+                load_frag(stab[k], u, b, zc);
+              }
+              f32x4 lo, hi;
+#pragma unroll
+              for (int j = 0; j < 4; ++j) {
+                lo[j] = c0 + j < D.Dm ? raw[b][u][j] : 0.f;
+                hi[j] = c0 + 4 + j < D.Dm ? raw[b][u][4 + j] : 0.f;
+              }
+              const Frag f = P::pack(lo, hi);
+              xk[b][s] = (c0 >= 0 && okr[b]) ? f : xk[b][s];
+            }
+          }
+        }
+        // (the previous scenario's weights are stored here, ahead of the prefetch: stores and loads
+        // share one in-order counter, so a store issued after the loads would be waited for with them)
+        if (PRE && k > 0) store_w(k - 1, wp);
+        if (PRE && ins) load_rows(stab[min(k + 1, A.K - 1)], zc);   // the next scenario's rows, in flight during the tower
+
+        auto l0 = [&](f32x4 (&a)[2][4]) {
+          f32x4 init[2][4];
+          bias_init<4>(auxt + D.a_sb, init);
+          layer0<P, KS1, 4>(ldt, D.s_fwd0, xk, init, a);
+        };
+        float w[2];
+        sdf_forward_tile<P, false>(ldt, auxt, Dt, kw, l0, w);
+        if (PRE) { wp[0] = w[0]; wp[1] = w[1]; }
+        else store_w(k, w);
+      }
+      if (PRE) store_w(A.K - 1, wp);
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void k_knock_macro_fill(KnockFillArgs a) {
+  const int u = blockIdx.y, MW = (a.M + 31) / 32;
+  const size_t n = (size_t)a.T * a.M;
+  const auto mk = gp(a.masks) + (size_t)u * MW;
+  const auto out = gp(a.out) + (size_t)u * a.stride;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const int j = (int)(i % (size_t)a.M);
+    const bool rep = (mk[j >> 5] >> (j & 31)) & 1u;
+    out[i] = rep ? gp(a.base)[j] : gp(a.macro)[i];
   }
 }
 
@@ -246,6 +435,47 @@ void launch_knock_fwd(const MlpJob* jobs, const KnockArgs& A, const MlpDims& D0,
   if (D.fp32) { KNOCK_KS(PrecF32, 2) KNOCK_KS(PrecF32, 4) }
   else { KNOCK_KS(PrecBF16, 2) KNOCK_KS(PrecBF16, 4) }
 #undef KNOCK_KS
+  HIP_OK(hipGetLastError());
+}
+
+bool knock_pp_supported(const MlpDims& D0, int KS1, int T) {
+  return knock_supported(D0, KS1, T) && knock_pp_lds_bytes(knock_pp_dims(D0), KS1) <= 160 * 1024;
+}
+
+void launch_knock_fwd_pp(const MlpJob* jobs, const KnockPpArgs& B, const MlpDims& D0, int KS1, hipStream_t st) {
+  const KnockArgs& A = B.a;
+  if (!knock_pp_supported(D0, KS1, A.T) || A.R <= 0 || A.G <= 0 || A.K < 1 || A.K > KNOCK_MAX_CHUNK ||
+      (D0.Dm > 0 && !B.tabs))
+    dlap_throw_hip(hipErrorInvalidValue, "knockout_macro: unsupported shape", __FILE__, __LINE__);
+  const MlpDims D = knock_pp_dims(D0);
+  const size_t sh = knock_pp_lds_bytes(D, KS1);
+  const int ntiles = (A.R + 31) >> 5;
+  dim3 grid((ntiles + 4 * kTPW - 1) / (4 * kTPW)), block(256);
+  // the trailing k-steps with per-period columns (header of k_knock_fwd_pp); none with Dm = 0
+  const int NS = std::max(1, KS1 - D.ppc / 32);
+  // (the build without the prefetch keeps to the 4-byte loads: its register budget)
+  const bool vec = D.Dm > 0 && (D.Dm & 3) == 0;
+#define KNOCK_PP1(PP, KS, N, PRE, VEC) hipLaunchKernelGGL((k_knock_fwd_pp<PP, KS, N, PRE, VEC>), grid, block, sh, st, jobs, B, D);
+#define KNOCK_PP(PP, KS, N) if (vec) { KNOCK_PP1(PP, KS, N, true, true) } else { KNOCK_PP1(PP, KS, N, true, false) }
+  if (D.fp32) {
+    if (KS1 == 2) { if (NS == 1) { KNOCK_PP(PrecF32, 2, 1) } else { KNOCK_PP(PrecF32, 2, 2) } }
+    else if (NS == 1) { KNOCK_PP(PrecF32, 4, 1) } else if (NS == 2) { KNOCK_PP(PrecF32, 4, 2) }
+    else { KNOCK_PP1(PrecF32, 4, 4, false, false) }
+  } else {          // (128-column bf16 rows: two waves per SIMD leave room for one k-step's rows in flight)
+    if (KS1 == 2) { if (NS == 1) { KNOCK_PP(PrecBF16, 2, 1) } else { KNOCK_PP(PrecBF16, 2, 2) } }
+    else if (NS == 1) { KNOCK_PP(PrecBF16, 4, 1) } else { KNOCK_PP1(PrecBF16, 4, 4, false, false) }
+  }
+#undef KNOCK_PP1
+#undef KNOCK_PP
+  HIP_OK(hipGetLastError());
+}
+
+void launch_knock_macro_fill(const KnockFillArgs& A, hipStream_t st) {
+  if (A.U < 1 || A.U > 65535 || A.T < 1 || A.M < 1 || (A.stride & 3) || A.stride < (size_t)A.T * A.M)
+    dlap_throw_hip(hipErrorInvalidValue, "knockout_macro: unsupported arguments", __FILE__, __LINE__);
+  const size_t n = (size_t)A.T * A.M;
+  const unsigned gx = (unsigned)std::min<size_t>((n + 255) / 256, 1024);
+  hipLaunchKernelGGL(k_knock_macro_fill, dim3(gx, (unsigned)A.U), dim3(256), 0, st, A);
   HIP_OK(hipGetLastError());
 }
 

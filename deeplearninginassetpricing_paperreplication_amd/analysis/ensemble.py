@@ -100,7 +100,8 @@ def evaluate_ensemble(checkpoint_dirs: Sequence[str], data_dir: str, device: str
                       prediction_out: str = None, benchmark_ipca: bool = False, ipca_factors=(1, 2, 3, 4, 5, 6),
                       ipca_intercept: bool = True, fama_macbeth: bool = False, fm_out: str = None,
                       knockout: bool = False, knockout_split: str = "test", knockout_groups=None,
-                      knockout_base="zero", knockout_xs_r2: bool = False, knockout_out: str = None) -> Dict:
+                      knockout_base="zero", knockout_xs_r2: bool = False, knockout_out: str = None,
+                      knockout_macro: bool = False, knockout_macro_groups=None, knockout_macro_base="zero") -> Dict:
     """Reference output and return value; ``paper=True`` (CLI ``--paper_metrics``) adds the
     paper's EV / XS-R² / turnover / max 1-month loss of the ensemble's SDF factor per split;
     ``importance=True`` (CLI ``--variable_importance``) adds the sensitivity ranking of the
@@ -147,7 +148,10 @@ def evaluate_ensemble(checkpoint_dirs: Sequence[str], data_dir: str, device: str
     entry of ``knockout_groups``, a dict or the CLI's JSON file of name -> columns or names; ``knockout_base``:
     ``zero``, ``median`` or an [F] array; ``knockout_xs_r2`` adds XS-R²) under the key ``knockout``, prints
     one table (scenario, Sharpe, d Sharpe, EV, d EV) and writes the report to ``knockout_out`` (JSON) when
-    given."""
+    given; ``knockout_macro=True`` (CLI ``--knockout_macro``, with ``knockout``) adds one scenario per macro
+    series held at ``knockout_macro_base`` (``zero``: the training mean, ``median`` or an [M] array) over the
+    whole split, through the LSTM, and ``knockout_macro_groups`` (a dict or the CLI's JSON file of name ->
+    series or names) one per group; the table labels them by the names the macro importance report uses."""
     say = print if verbose else (lambda *a, **k: None)
     bar = "=" * 70
     say(bar); say(f"ENSEMBLE EVALUATION ({len(checkpoint_dirs)} models, averaged weights)"); say(bar); say()
@@ -377,10 +381,17 @@ def evaluate_ensemble(checkpoint_dirs: Sequence[str], data_dir: str, device: str
             raise ValueError(f"knockout_split must be one of {SPLITS}")
         ds = datasets[SPLITS.index(knockout_split)]
         groups = ko.load_groups(knockout_groups) if isinstance(knockout_groups, str) else knockout_groups
+        mkw = {}
+        if knockout_macro or knockout_macro_groups:
+            mg = ko.load_groups(knockout_macro_groups) if isinstance(knockout_macro_groups, str) else knockout_macro_groups
+            mkw = dict(macro=bool(knockout_macro), macro_groups=mg, macro_base=knockout_macro_base,
+                       macro_names=getattr(ds, "macro_names", None))
         rep = ko.knockout_importance(models, batches[knockout_split], groups=groups, base=knockout_base,
-                                     xs_r2=knockout_xs_r2, device=device, names=getattr(ds, "variable_names", None))
+                                     xs_r2=knockout_xs_r2, device=device, names=getattr(ds, "variable_names", None),
+                                     **mkw)
         out["knockout"] = rep
-        say(bar); say(f"CHARACTERISTIC KNOCK-OUTS ({knockout_split} split, ensemble SDF, {rep['path']} path)")
+        what = "CHARACTERISTIC AND MACRO KNOCK-OUTS" if "macro_columns" in rep else "CHARACTERISTIC KNOCK-OUTS"
+        say(bar); say(f"{what} ({knockout_split} split, ensemble SDF, {rep['path']} path)")
         say(bar); say()
         for line in ko.format_knockout(rep):
             say(line)
@@ -451,6 +462,12 @@ def _parser():
     p.add_argument("--knockout_base", type=str, default="zero", choices=("zero", "median"))
     p.add_argument("--knockout_xs_r2", action="store_true", help="with --knockout: also XS-R2 per scenario")
     p.add_argument("--knockout_out", type=str, default=None, help="write the knock-out report to FILE.json")
+    p.add_argument("--knockout_macro", action="store_true",
+                   help="with --knockout: also one scenario per macro series, held constant over the split, through the LSTM")
+    p.add_argument("--knockout_macro_groups", type=str, default=None,
+                   help="with --knockout: FILE.json: {group name: [macro series or names]}, one scenario per group")
+    p.add_argument("--knockout_macro_base", type=str, default="zero", choices=("zero", "median"),
+                   help="with --knockout: the value a knocked-out series is held at (zero: the training mean)")
     return p
 
 
@@ -482,9 +499,14 @@ def _extra_kwargs(a) -> Dict:
         kw.update(benchmark_ipca=True, ipca_factors=tuple(a.ipca_factors), ipca_intercept=not a.ipca_no_intercept)
     if a.fama_macbeth:
         kw.update(fama_macbeth=True, fm_out=a.fm_out, sort_split=a.sort_split, ipca_intercept=not a.ipca_no_intercept)
+    if (a.knockout_macro or a.knockout_macro_groups or a.knockout_macro_base != "zero") and not a.knockout:
+        raise SystemExit("--knockout_macro, --knockout_macro_groups and --knockout_macro_base need --knockout")
     if a.knockout:
         kw.update(knockout=True, knockout_split=a.knockout_split, knockout_groups=a.knockout_groups,
                   knockout_base=a.knockout_base, knockout_xs_r2=a.knockout_xs_r2, knockout_out=a.knockout_out)
+        if a.knockout_macro or a.knockout_macro_groups:
+            kw.update(knockout_macro=a.knockout_macro, knockout_macro_groups=a.knockout_macro_groups,
+                      knockout_macro_base=a.knockout_macro_base)
     return kw
 
 

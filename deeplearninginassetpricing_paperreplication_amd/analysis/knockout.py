@@ -41,8 +41,32 @@ intermediate. Mixed-architecture ensembles and shapes the kernel does not cover 
 path) fall back to the CPU path with a printed note; a split the engine cannot hold (more periods
 than it accepts, and ``Engine.knockout`` itself takes at most 65535) raises ``ValueError``.
 
-Out of scope: knocking out state columns or macro series, retraining without a characteristic, the
-moment network, multi-rank runs, a shipped category map (the groups file is the user's).
+Macro knock-outs (``macro=True``, ``macro_groups``, ``extra_scenarios``). A scenario also holds a set
+``Q_k`` of macro series in ``0..M-1`` and the shared base row ``macro_base[0..M-1]``. The counterfactual
+split has ``x^k`` as above and
+
+    m^k[t][j] = macro_base[j]  for j in Q_k, every period t of the split;   m[t][j] otherwise
+    pp_g^k    = member g's evaluation LSTM run over m^k[0..T-1] from the state the split's evaluation
+                starts from, every layer, evaluation mode; without an LSTM pp_g^k[t] = m^k[t]
+    w_g       = raw tower output on (x^k, pp_g^k)           -- everything after this line is as above
+
+``macro`` is the standardised series the model is fed, so ``macro_base="zero"`` (the default) is the
+training mean; ``"median"`` is the per-series median over the split's periods; or an ``[M]`` array. A
+knock-out holds a series constant over the whole split: the question is what the trained ensemble does
+in a world where the series carries no information. The moment network, the train statistics and the
+split's length are untouched. The scenario order is: baseline, characteristic singles, characteristic
+groups, macro singles, macro groups, ``extra_scenarios`` -- ``(label, columns, macro_columns)``, the
+only way to a scenario that replaces characteristics and series together. When a macro scenario is
+present the report gains ``macro_columns`` (one list per scenario) and ``macro_base``; without one it is
+key for key and bit for bit the characteristic report. ``device="cuda"`` then runs
+``Engine.knockout_macro``: per (scenario, member) the forward's own projection and recurrence kernels
+over the altered series, and ``k_knock_fwd_pp``, which inserts the scenario's per-period table into
+tiles it loaded once. A model set without macro input raises ``ValueError``.
+
+Out of scope: knock-outs over a window of periods or at a lag, knocking out the LSTM state columns of
+an LSTM model, sharing a recurrence between scenarios, the moment network and its LSTM, retraining
+without a characteristic or a series, multi-rank runs, a shipped category map (the groups file is the
+user's).
 """
 from __future__ import annotations
 
@@ -96,6 +120,67 @@ def build_scenarios(F: int, groups=None, names: Optional[Sequence] = None, singl
     return labels, cols
 
 
+def _macro_column(tok, M: int, idx: Dict[str, int]) -> int:
+    if isinstance(tok, str):
+        if tok in idx:
+            return idx[tok]
+        try:
+            c = int(tok)
+        except ValueError:
+            raise ValueError(f"knockout: unknown macro series {tok!r}") from None
+    else:
+        c = int(tok)
+    if c < 0 or c >= M:
+        raise ValueError(f"knockout: macro series {c} outside [0, {M})")
+    return c
+
+
+def macro_series_names(M: int, macro_names: Optional[Sequence] = None) -> List[str]:
+    """The names the macro importance report uses: ``macro_names`` when it has M entries, else macro0.."""
+    return [str(n) for n in macro_names] if macro_names is not None and len(macro_names) == M \
+        else [f"macro{j}" for j in range(M)]
+
+
+def build_macro_scenarios(M: int, macro_groups=None, macro_names: Optional[Sequence] = None, singles: bool = True):
+    """(labels, macro_columns): one scenario per macro series (``singles``), one per group; no baseline."""
+    nm = macro_series_names(M, macro_names)
+    idx = {n: j for j, n in enumerate(nm)}
+    labels, cols = [], []
+    if singles:
+        labels += nm
+        cols += [(j,) for j in range(M)]
+    if macro_groups:
+        if not isinstance(macro_groups, dict):
+            raise ValueError("knockout: macro_groups must map a name to a list of series or names")
+        for g, members in macro_groups.items():
+            if isinstance(members, (str, int)) or len(members) == 0:
+                raise ValueError(f"knockout: macro group {g!r} must be a non-empty list of series or names")
+            labels.append(str(g))
+            cols.append(tuple(sorted({_macro_column(m, M, idx) for m in members})))
+    return labels, cols
+
+
+def _macro_dim(batch: Dict) -> int:
+    mac = batch.get("macro_features")
+    return 0 if mac is None else int(mac.shape[-1])
+
+
+def resolve_macro_base(macro_base, batch: Dict) -> np.ndarray:
+    M = _macro_dim(batch)
+    if isinstance(macro_base, str):
+        if macro_base == "zero":
+            return np.zeros(M)
+        if macro_base == "median":
+            mac = batch["macro_features"]
+            mac = mac.cpu().numpy() if isinstance(mac, torch.Tensor) else np.asarray(mac)
+            return np.median(mac.astype(np.float64), axis=0) if mac.shape[0] else np.zeros(M)
+        raise ValueError("knockout: macro_base must be 'zero', 'median' or an [M] array")
+    b = np.asarray(macro_base, dtype=np.float64).ravel()
+    if len(b) != M:
+        raise ValueError(f"knockout: macro_base must have M = {M} entries")
+    return b
+
+
 def resolve_base(base, batch: Dict) -> np.ndarray:
     F = int(batch["individual_features"].shape[-1])
     if isinstance(base, str):
@@ -119,6 +204,17 @@ def scenario_masks(cols: Sequence[Sequence[int]], F: int) -> np.ndarray:
             if c < 0 or c >= F:
                 raise ValueError(f"knockout: column {c} outside [0, {F})")
             m[k, c // 32] |= np.uint32(1 << (c % 32))
+    return m
+
+
+def macro_scenario_masks(macro_cols: Sequence[Sequence[int]], M: int) -> np.ndarray:
+    """uint32 [K][ceil(M / 32)]: bit j % 32 of word j / 32 is set for the macro series of the scenario."""
+    m = np.zeros((len(macro_cols), (M + 31) // 32), dtype=np.uint32)
+    for k, q in enumerate(macro_cols):
+        for j in q:
+            if j < 0 or j >= M:
+                raise ValueError(f"knockout: macro series {j} outside [0, {M})")
+            m[k, j // 32] |= np.uint32(1 << (j % 32))
     return m
 
 
@@ -194,11 +290,18 @@ def metrics_from_knockout_sums(sums: Dict, dense=None, returns=None, mask=None) 
 
 
 # ---- the two paths ------------------------------------------------------------------------------
-def raw_weights_cpu(ms, batch, cols: Sequence[int], base: np.ndarray, dtype) -> np.ndarray:
-    """[G][T][N] raw tower outputs of the (prepared) models on the batch with ``cols`` set to base."""
+def raw_weights_cpu(ms, batch, cols: Sequence[int], base: np.ndarray, dtype, macro_cols: Sequence[int] = (),
+                    macro_base: Optional[np.ndarray] = None) -> np.ndarray:
+    """[G][T][N] raw tower outputs of the (prepared) models on the batch with ``cols`` set to base and
+    the macro series ``macro_cols`` set to ``macro_base`` in every period."""
     feats = batch["individual_features"].to(dtype)
     macro = batch.get("macro_features")
     macro = None if macro is None else macro.to(dtype)
+    if len(macro_cols):
+        if macro is None:
+            raise ValueError("knockout: a macro scenario needs macro_features")
+        macro = macro.clone()
+        macro[:, list(macro_cols)] = torch.as_tensor(np.asarray(macro_base)[list(macro_cols)]).to(dtype)
     T, N, F = feats.shape
     x = feats
     if len(cols):
@@ -213,15 +316,15 @@ def raw_weights_cpu(ms, batch, cols: Sequence[int], base: np.ndarray, dtype) -> 
     return np.stack(out)
 
 
-def _cpu_sums(models, batch, cols, base, dtype, dense: bool) -> Dict:
+def _cpu_sums(models, batch, cols, base, dtype, dense: bool, macro_cols=None, macro_base=None) -> Dict:
     cpu = {k: (v.cpu() if isinstance(v, torch.Tensor) else v) for k, v in batch.items()}
     ms = [copy.deepcopy(m).cpu().to(dtype).eval() for m in models]
     norm = [bool(m.sdf_net.normalize_weights) for m in ms]
     nd = np.float32 if dtype == torch.float32 else np.float64
     ret, mask = cpu["returns"].numpy(), cpu["mask"].bool().numpy()
     parts = []
-    for cs in cols:                                 # one scenario at a time: [1][G][T][N] in memory
-        w = raw_weights_cpu(ms, cpu, cs, base, dtype)
+    for k, cs in enumerate(cols):                   # one scenario at a time: [1][G][T][N] in memory
+        w = raw_weights_cpu(ms, cpu, cs, base, dtype, macro_cols[k] if macro_cols else (), macro_base)
         parts.append(knockout_sums_numpy(w[None], ret, mask, norm, nd, dense))
     out = {k: parts[0][k] for k in ("n", "sum_r", "sum_rr")}
     for k in SUM_KEYS + (("dense",) if dense else ()):
@@ -229,8 +332,10 @@ def _cpu_sums(models, batch, cols, base, dtype, dense: bool) -> Dict:
     return out
 
 
-def _gpu_sums(models, batch, cols, base, precision: str, dense: bool) -> Optional[Dict]:
-    """The same sums from the native engine, or None (with a printed note) where it does not apply."""
+def _gpu_sums(models, batch, cols, base, precision: str, dense: bool, macro_cols=None, macro_base=None) -> Optional[Dict]:
+    """The same sums from the native engine, or None (with a printed note) where it does not apply.
+    ``Engine.knockout_macro`` is used only when a macro scenario is present."""
+    has_macro = bool(macro_cols) and any(len(q) for q in macro_cols)
     if len({m.spec for m in models}) != 1:
         print("[knockout] mixed-architecture ensemble: using the CPU path")
         return None
@@ -248,11 +353,21 @@ def _gpu_sums(models, batch, cols, base, precision: str, dense: bool) -> Optiona
         if not e.knockout_supported(0):
             print("[knockout] knockout: not available for this shape: using the CPU path")
             return None
+        if has_macro and not e.knockout_macro_supported(0):
+            print("[knockout] knockout_macro: not available for this shape: using the CPU path")
+            return None
         wd = torch.zeros(K, T, N, dtype=torch.float32, device=dev) if dense else None
         torch.cuda.synchronize(dev)
         try:
-            r = e.knockout(0, scenario_masks(cols, F), K, [float(x) for x in np.asarray(base, dtype=np.float32)],
-                           wd.data_ptr() if dense else 0)
+            if has_macro:
+                M = _macro_dim(batch)
+                r = e.knockout_macro(0, scenario_masks(cols, F), macro_scenario_masks(macro_cols, M), K,
+                                     [float(x) for x in np.asarray(base, dtype=np.float32)],
+                                     [float(x) for x in np.asarray(macro_base, dtype=np.float32)],
+                                     wd.data_ptr() if dense else 0)
+            else:
+                r = e.knockout(0, scenario_masks(cols, F), K, [float(x) for x in np.asarray(base, dtype=np.float32)],
+                               wd.data_ptr() if dense else 0)
         except ValueError as err:
             print(f"[knockout] {err}: using the CPU path")
             return None
@@ -260,6 +375,8 @@ def _gpu_sums(models, batch, cols, base, precision: str, dense: bool) -> Optiona
         e.sync()
     out = {k: np.asarray(r[k], dtype=np.float64) for k in ("n", "sum_r", "sum_rr") + SUM_KEYS}
     out["gpu_ms"] = (float(r["fwd_ms"]), float(r["reduce_ms"]))
+    if has_macro:
+        out["gpu_ms"] += (float(r["lstm_ms"]),)
     if dense:
         out["dense"] = wd.cpu().numpy()
     return out
@@ -267,24 +384,56 @@ def _gpu_sums(models, batch, cols, base, precision: str, dense: bool) -> Optiona
 
 def knockout_importance(models: Sequence, batch: Dict, groups=None, base="zero", xs_r2: bool = False,
                         device: str = "cpu", precision: str = "bf16", dtype: torch.dtype = torch.float32,
-                        names: Optional[Sequence] = None, singles: bool = True) -> Dict:
+                        names: Optional[Sequence] = None, singles: bool = True, macro: bool = False,
+                        macro_groups=None, macro_base="zero", macro_names: Optional[Sequence] = None,
+                        macro_singles: bool = True, extra_scenarios=None) -> Dict:
     """The knock-out report of the ensemble over ``batch`` (module docstring): ``scenarios`` (labels),
     ``columns``, ``sharpe`` / ``ev`` / ``xs_r2`` [K] (``xs_r2`` None unless asked for), ``member_sharpes``
     [K][G], ``d_sharpe`` / ``d_ev`` / ``d_xs_r2`` (scenario minus baseline), ``factor`` [K][T],
     ``ranking`` (the scenarios other than the baseline, largest Sharpe loss first), ``base`` and
-    ``path`` (``"engine"`` or ``"cpu"``). ``precision`` applies to the engine, ``dtype`` to the CPU path."""
+    ``path`` (``"engine"`` or ``"cpu"``). ``precision`` applies to the engine, ``dtype`` to the CPU path.
+    ``macro=True`` adds one scenario per macro series (``macro_singles``) and one per entry of
+    ``macro_groups``; ``extra_scenarios`` a list of ``(label, columns, macro_columns)``. With a macro
+    scenario present the report also has ``macro_columns`` and ``macro_base`` (module docstring)."""
     models = list(models)
     if not models:
         raise ValueError("no models")
     F = int(batch["individual_features"].shape[-1])
     labels, cols = build_scenarios(F, groups, names, singles)
     b = resolve_base(base, batch)
+    qcols, mb = None, None
+    if macro or macro_groups or extra_scenarios:
+        M = _macro_dim(batch)
+        qcols = [()] * len(cols)
+        no_macro = M == 0 or any(int(m.sdf_net.macro_dim) == 0 for m in models)
+        if (macro or macro_groups) and no_macro:
+            raise ValueError("knockout: a macro scenario needs models with macro input (macro_feature_dim > 0)")
+        if macro or macro_groups:
+            ql, qc = build_macro_scenarios(M, macro_groups, macro_names, macro_singles and bool(macro))
+            labels, cols, qcols = labels + ql, cols + [()] * len(qc), qcols + qc
+        if extra_scenarios:
+            cn = [str(n) for n in names] if names is not None and len(names) == F else [f"x{j}" for j in range(F)]
+            cidx = {n: j for j, n in enumerate(cn)}
+            midx = {n: j for j, n in enumerate(macro_series_names(M, macro_names))}
+            for item in extra_scenarios:
+                if len(item) != 3:
+                    raise ValueError("knockout: an extra scenario is (label, columns, macro_columns)")
+                lab, cs, qs = item
+                labels.append(str(lab))
+                cols.append(tuple(sorted({_column(c, F, cidx) for c in cs})))
+                qcols.append(tuple(sorted({_macro_column(q, M, midx) for q in qs})))
+        if any(len(q) for q in qcols):
+            if no_macro:
+                raise ValueError("knockout: a macro scenario needs models with macro input (macro_feature_dim > 0)")
+            mb = resolve_macro_base(macro_base, batch)
+        else:
+            qcols = None
     sums = None
     if str(device).startswith("cuda"):
-        sums = _gpu_sums(models, batch, cols, b, precision, xs_r2)
+        sums = _gpu_sums(models, batch, cols, b, precision, xs_r2, qcols, mb)
     path = "engine" if sums is not None else "cpu"
     if sums is None:
-        sums = _cpu_sums(models, batch, cols, b, dtype, xs_r2)
+        sums = _cpu_sums(models, batch, cols, b, dtype, xs_r2, qcols, mb)
     ret = batch["returns"].cpu().numpy() if isinstance(batch["returns"], torch.Tensor) else np.asarray(batch["returns"])
     msk = batch["mask"].cpu().numpy() if isinstance(batch["mask"], torch.Tensor) else np.asarray(batch["mask"])
     met = metrics_from_knockout_sums(sums, sums.get("dense"), ret, msk)
@@ -293,6 +442,9 @@ def knockout_importance(models: Sequence, batch: Dict, groups=None, base="zero",
            "d_sharpe": met["sharpe"] - met["sharpe"][0], "d_ev": met["ev"] - met["ev"][0],
            "d_xs_r2": None if met["xs_r2"] is None else met["xs_r2"] - met["xs_r2"][0],
            "base": b, "path": path, "sums": {k: sums[k] for k in ("n", "sum_r", "sum_rr") + SUM_KEYS}}
+    if qcols is not None:
+        out["macro_columns"] = [list(q) for q in qcols]
+        out["macro_base"] = mb
     rest = np.arange(1, len(labels))
     out["ranking"] = [int(k) for k in rest[np.argsort(out["d_sharpe"][1:], kind="stable")]]
     return out
