@@ -47,6 +47,7 @@
 #include "qsort2.h"
 #include "linport.h"
 #include "xgram.h"
+#include "xrank.h"
 #include "pred.h"
 #include "rnn.h"
 #include "update.h"
@@ -3650,6 +3651,19 @@ PYBIND11_MODULE(_dlap_hip, m) {
                           reinterpret_cast<float*>(port_ind), reinterpret_cast<hipStream_t>(stream));
         },
         "K11: ensemble portfolio [T] and individual portfolios [G][T] from gathered weights (device pointers)");
+  m.def("rank_characteristics",
+        [](uintptr_t x, uintptr_t rowok, uintptr_t out, uintptr_t cnt, long long T, int N, int F, float thr,
+           float fill_missing, float fill_dead, uintptr_t stream) {
+          launch_xrank(reinterpret_cast<const float*>(x), reinterpret_cast<const uint8_t*>(rowok),
+                       reinterpret_cast<float*>(out), reinterpret_cast<int*>(cnt), T, N, F, thr, fill_missing,
+                       fill_dead, reinterpret_cast<hipStream_t>(stream));
+        },
+        py::arg("x"), py::arg("rowok"), py::arg("out"), py::arg("cnt"), py::arg("T"), py::arg("N"), py::arg("F"),
+        py::arg("thr"), py::arg("fill_missing"), py::arg("fill_dead"), py::arg("stream") = 0,
+        "cross-sectional rank transform of a dense fp32 chunk [T][N][F] (device pointers; out may be x)");
+  m.def("rank_supported", [](int N) { return xrank_supported(N); });
+  m.def("rank_block_keys", []() { return xrank_block_keys(); });
+  m.attr("XRANK_MAX_N") = (int)XRANK_MAX_N;
   m.attr("HIST_W") = (int)HIST_W;
   m.attr("SC_NSCAL") = (int)SC_NSCAL;
 }
