@@ -45,6 +45,7 @@
 #include "panel.h"
 #include "qsort.h"
 #include "qsort2.h"
+#include "qtree.h"
 #include "linport.h"
 #include "xgram.h"
 #include "xrank.h"
@@ -1005,6 +1006,67 @@ class Engine {
     }
     py::dict d;
     d["count"] = cnt; d["sum"] = sum; d["breaks_a"] = bra; d["breaks_b"] = brb; d["rows"] = D.R; d["gpu_ms"] = ms;
+    return d;
+  }
+  // Tree-sorted portfolios of split s (k_qtree.hip, definition and layout in qtree.h): per period
+  // and tree (c_1, .., c_D) of key indices, D = splits.size() nested conditional quantile splits
+  // (splits[l-1] = Q_l children per node of level l - 1), every node of every level a portfolio.
+  // Key indices, extra_keys, values and the panel-only property as for double_sorted_portfolios;
+  // every tree of a call has length D. With L = Q_1 .. Q_D <= 36 leaves, NN nodes and NB = L - 1
+  // breakpoints it returns count int32 [T][P][NN], sum fp64 [T][P][NN][1 + n_values], breaks fp32
+  // [T][P][NB] (NaN where the period or the node is empty), level_offsets [D+2] (node (l, j) at
+  // level_offsets[l] + j), break_offsets [D+1] (breakpoint (l, a, d) at break_offsets[l-1] +
+  // a (Q_l - 1) + d - 1), rows (= R) and gpu_ms. An empty tree list returns empty arrays and
+  // launches nothing.
+  py::dict tree_sorted_portfolios(int s, std::vector<std::vector<int>> trees, std::vector<int> splits,
+                                  uintptr_t extra_keys, int n_extra, uintptr_t values, int n_values) {
+    check_split(s, "tree_sorted_portfolios", kSplitIndex);
+    const int Dp = (int)splits.size();
+    if (Dp < 1 || Dp > QTREE_MAX_D) throw std::invalid_argument("tree_sorted_portfolios: splits must have 1 to 5 levels");
+    for (int q : splits)
+      if (q < 2 || q > QTREE_MAX_Q) throw std::invalid_argument("tree_sorted_portfolios: every split must be in [2, 16]");
+    int off[QTREE_MAX_D + 2], boff[QTREE_MAX_D + 1];
+    if (!qtree_layout(splits.data(), Dp, off, boff))
+      throw std::invalid_argument("tree_sorted_portfolios: the product of the splits must be at most 36");
+    if (n_values < 0 || n_values > QTREE_MAX_VALUES) throw std::invalid_argument("tree_sorted_portfolios: n_values must be in [0, 2]");
+    if (n_extra < 0 || (n_extra > 0 && !extra_keys)) throw std::invalid_argument("tree_sorted_portfolios: n_extra needs extra_keys");
+    if (n_values > 0 && !values) throw std::invalid_argument("tree_sorted_portfolios: n_values needs values");
+    for (const auto& tr : trees) {
+      if ((int)tr.size() != Dp) throw std::invalid_argument("tree_sorted_portfolios: every tree needs one key per level of splits");
+      for (int c : tr)
+        if (c < 0 || c >= md_.F + n_extra) throw std::invalid_argument("tree_sorted_portfolios: key index outside [0, F + n_extra)");
+    }
+    const SplitDev& D = check_split(s, "tree_sorted_portfolios", kSplitSet | kSplitPeriods);
+    const int K1 = 1 + n_values, P = (int)trees.size(), NN = off[Dp + 1], NB = boff[Dp];
+    auto cnt = filled<int>({D.T, P, NN}, 0);
+    auto sum = filled<double>({D.T, P, NN, K1}, 0.0);
+    auto brk = filled<float>({D.T, P, NB}, std::nanf(""));
+    float ms = 0.f;
+    if (D.R > 0 && D.T > 0 && P > 0) {        // (an empty split or tree list launches nothing)
+      std::vector<int> flat;
+      for (const auto& tr : trees) flat.insert(flat.end(), tr.begin(), tr.end());
+      DevBuf<int> dtrees, dcnt;
+      DevBuf<double> dsum;
+      DevBuf<float> dbrk;
+      up(dtrees, flat.data(), flat.size());
+      dcnt.alloc((size_t)cnt.size(), false); dsum.alloc((size_t)sum.size(), false); dbrk.alloc((size_t)brk.size(), false);
+      QtreeArgs A{};
+      A.pv = panel_view(D);
+      A.P = P; A.trees = dtrees.p; A.D = Dp;
+      for (int l = 0; l < Dp; ++l) A.Q[l] = splits[l];
+      A.E = n_extra; A.extra = reinterpret_cast<const float*>(extra_keys);
+      A.K = n_values; A.values = reinterpret_cast<const float*>(values);
+      A.count = dcnt.p; A.sum = dsum.p; A.breaks = dbrk.p;
+      ms = timed([&] { launch_qtree_port(A, st_); });
+      fetch(cnt, dcnt.p);
+      fetch(sum, dsum.p);
+      fetch(brk, dbrk.p);
+    }
+    py::dict d;
+    d["count"] = cnt; d["sum"] = sum; d["breaks"] = brk;
+    d["level_offsets"] = std::vector<int>(off, off + Dp + 2);
+    d["break_offsets"] = std::vector<int>(boff, boff + Dp + 1);
+    d["rows"] = D.R; d["gpu_ms"] = ms;
     return d;
   }
   // Linear benchmark SDFs of split s (k_linport.hip, definitions in linport.h and
@@ -3595,6 +3657,9 @@ PYBIND11_MODULE(_dlap_hip, m) {
       .def("double_sorted_portfolios", &Engine::double_sorted_portfolios, py::arg("s"), py::arg("pairs"),
            py::arg("qa") = 5, py::arg("qb") = 5, py::arg("conditional") = true, py::arg("extra_keys") = 0,
            py::arg("n_extra") = 0, py::arg("values") = 0, py::arg("n_values") = 0)
+      .def("tree_sorted_portfolios", &Engine::tree_sorted_portfolios, py::arg("s"), py::arg("trees"),
+           py::arg("splits"), py::arg("extra_keys") = 0, py::arg("n_extra") = 0, py::arg("values") = 0,
+           py::arg("n_values") = 0)
       .def("managed_portfolios", &Engine::managed_portfolios, py::arg("s"))
       .def("linear_portfolios", &Engine::linear_portfolios, py::arg("s"), py::arg("theta"),
            py::arg("center") = py::none(), py::arg("w_out") = 0)

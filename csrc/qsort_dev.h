@@ -1,5 +1,6 @@
-// Device helpers shared by the quantile-sort kernels (k_qsort.hip, k_qsort2.hip): the
-// order-preserving float -> uint32 key map and the key load from the compacted panel.
+// Device helpers shared by the quantile-sort kernels (k_qsort.hip, k_qsort2.hip, k_qtree.hip): the
+// order-preserving float -> uint32 key map, the key load from the compacted panel and
+// (k_qtree.hip) the wave's step of the radix select.
 #pragma once
 #include "common.h"
 #include "panel_view.h"
@@ -28,4 +29,31 @@ DLAP_DEV uint32_t qkey_load(const PanelView& a, bool is_char, int col, const flo
   }
   const int i = gp(a.rowti)[r].y;
   return qkey_u32(gp(ext)[i]);
+}
+
+// One wave's step of the multi-level radix select (k_qsort2.hip's scan): the histogram h of
+// nbins <= 256 bins holds the rows of a breakpoint's group by their digit at this level, rk is the
+// breakpoint's residual rank within the group (rk < the group's rows). Exactly one lane finds the
+// bin that holds rank rk and returns true with dg = the bin, below = the rows in the bins below it
+// and in_bin = the rows in it. Lane l reads the bins 4 l .. 4 l + 3.
+DLAP_DEV bool qsel_wave_scan(const uint32_t* h, int nbins, uint32_t rk, int lane, uint32_t& dg, uint32_t& below,
+                             uint32_t& in_bin) {
+  const int b0 = 4 * lane;
+  const uint32_t c0 = b0 < nbins ? h[b0] : 0u, c1 = b0 + 1 < nbins ? h[b0 + 1] : 0u;
+  const uint32_t c2 = b0 + 2 < nbins ? h[b0 + 2] : 0u, c3 = b0 + 3 < nbins ? h[b0 + 3] : 0u;
+  const uint32_t sb = c0 + c1 + c2 + c3;
+  uint32_t inc = sb;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const uint32_t v = __shfl_up(inc, o, 64);
+    if (lane >= o) inc += v;
+  }
+  uint32_t cb = inc - sb;                              // rows in the bins below this lane's
+  if (!(cb <= rk && rk < inc)) return false;
+  dg = (uint32_t)b0; in_bin = c0;
+  if (rk >= cb + c0) { cb += c0; ++dg; in_bin = c1;
+    if (rk >= cb + c1) { cb += c1; ++dg; in_bin = c2;
+      if (rk >= cb + c2) { cb += c2; ++dg; in_bin = c3; } } }
+  below = cb;
+  return true;
 }

@@ -101,7 +101,9 @@ def evaluate_ensemble(checkpoint_dirs: Sequence[str], data_dir: str, device: str
                       ipca_intercept: bool = True, fama_macbeth: bool = False, fm_out: str = None,
                       knockout: bool = False, knockout_split: str = "test", knockout_groups=None,
                       knockout_base="zero", knockout_xs_r2: bool = False, knockout_out: str = None,
-                      knockout_macro: bool = False, knockout_macro_groups=None, knockout_macro_base="zero") -> Dict:
+                      knockout_macro: bool = False, knockout_macro_groups=None, knockout_macro_base="zero",
+                      tree_sorts=None, tree_chars=None, tree_depth: int = 3, tree_splits=2,
+                      tree_out: str = None) -> Dict:
     """Reference output and return value; ``paper=True`` (CLI ``--paper_metrics``) adds the
     paper's EV / XS-R² / turnover / max 1-month loss of the ensemble's SDF factor per split;
     ``importance=True`` (CLI ``--variable_importance``) adds the sensitivity ranking of the
@@ -151,7 +153,13 @@ def evaluate_ensemble(checkpoint_dirs: Sequence[str], data_dir: str, device: str
     given; ``knockout_macro=True`` (CLI ``--knockout_macro``, with ``knockout``) adds one scenario per macro
     series held at ``knockout_macro_base`` (``zero``: the training mean, ``median`` or an [M] array) over the
     whole split, through the LSTM, and ``knockout_macro_groups`` (a dict or the CLI's JSON file of name ->
-    series or names) one per group; the table labels them by the names the macro importance report uses."""
+    series or names) one per group; the table labels them by the names the macro importance report uses;
+    ``tree_sorts`` (CLI ``--tree_sorts``: a list of key sequences, or the CLI's comma list of ``A:B:C`` by
+    name, column or ``weight``) and / or ``tree_chars`` with ``tree_depth`` (CLI ``--tree_chars A,B,C
+    --tree_depth D``: every ordered sequence of ``D`` of these keys, the asset-pricing-tree set) add the
+    tree-sorted portfolios of ``sort_split`` (``analysis.tree_sorts``; ``tree_splits``: one integer for
+    every level or ``2x3x3``, at most 36 leaves and 4096 trees), priced by the SDF, under the key
+    ``tree_sorts`` and write them to ``tree_out`` (JSON) when given."""
     say = print if verbose else (lambda *a, **k: None)
     bar = "=" * 70
     say(bar); say(f"ENSEMBLE EVALUATION ({len(checkpoint_dirs)} models, averaged weights)"); say(bar); say()
@@ -279,6 +287,39 @@ def evaluate_ensemble(checkpoint_dirs: Sequence[str], data_dir: str, device: str
             with open(double_out, "w") as fh:
                 json.dump(sp.double_to_json(res_ds, priced), fh, indent=1)
             say(f"  Saved: {double_out}"); say()
+    if tree_sorts or tree_chars:
+        from . import tree_sorts as ts
+        if sort_split not in SPLITS:
+            raise ValueError(f"sort_split must be one of {SPLITS}")
+        ds = datasets[SPLITS.index(sort_split)]
+        b = batches[sort_split]
+        names = getattr(ds, "variable_names", None)
+        trees = ts.parse_trees(tree_sorts) if tree_sorts else []
+        if tree_chars:
+            chars = [c.strip() for c in tree_chars.split(",") if c.strip()] if isinstance(tree_chars, str) else list(tree_chars)
+            trees = trees + ts.all_trees(chars, tree_depth)
+        if not trees:
+            raise ValueError("tree sorts: no trees")
+        if len(trees) > ts.MAX_TREES:
+            raise ValueError(f"tree sorts: at most {ts.MAX_TREES} trees per call, got {len(trees)}")
+        splits = ts.parse_tree_splits(tree_splits, len(trees[0]))
+        if str(device).startswith("cuda"):
+            wavg = average_weights(list(wdev[sort_split].cpu().numpy()), np_batches[sort_split]["mask"])
+        else:
+            wavg = average_weights([w[sort_split] for w in weights], np_batches[sort_split]["mask"])
+        res_ts = ts.tree_sorted_portfolios(models, b, trees, splits=splits, device=device, names=names, weights=wavg)
+        priced = ts.price_tree_sorted(res_ts, wavg, np_batches[sort_split]["returns"], np_batches[sort_split]["mask"])
+        out["tree_sorts"] = {"portfolios": res_ts, "priced": priced}
+        sx = " x ".join(str(q) for q in res_ts["splits"])
+        say(bar); say(f"TREE-SORTED PORTFOLIOS ({sort_split} split, splits {sx}, equally weighted)")
+        say(bar); say()
+        for line in ts.format_tree_sorted(priced):
+            say(line)
+        say()
+        if tree_out:
+            with open(tree_out, "w") as fh:
+                json.dump(ts.tree_to_json(res_ts, priced), fh, indent=1)
+            say(f"  Saved: {tree_out}"); say()
     pred_json = {}
     if benchmark_ffn and not benchmarks:
         raise ValueError("benchmark_ffn needs benchmarks (CLI: --benchmark_ffn with --benchmarks)")
@@ -432,6 +473,14 @@ def _parser():
     p.add_argument("--double_quantiles", type=str, default="5x5", help="QAxQB buckets (2..16 each, at most 36 cells)")
     p.add_argument("--double_mode", type=str, default="conditional", choices=("conditional", "independent"))
     p.add_argument("--double_out", type=str, default=None, help="write the double-sorted results to FILE.json")
+    p.add_argument("--tree_sorts", type=str, default=None,
+                   help="tree-sorted portfolios on --sort_split: a comma list of A:B:C, by name, column index or 'weight'")
+    p.add_argument("--tree_chars", type=str, default=None,
+                   help="every ordered sequence of --tree_depth of these keys (a comma list), the asset-pricing-tree set")
+    p.add_argument("--tree_depth", type=int, default=3, help="depth of the --tree_chars trees (1..5)")
+    p.add_argument("--tree_splits", type=str, default="2",
+                   help="children per node: one integer for every level, or Q1xQ2x.. (2..16 each, at most 36 leaves)")
+    p.add_argument("--tree_out", type=str, default=None, help="write the tree-sorted results to FILE.json")
     p.add_argument("--benchmarks", action="store_true",
                    help="also evaluate the linear (LS) and elastic-net (EN) benchmark SDFs next to the ensemble")
     p.add_argument("--benchmark_grid", type=str, default="16x4", help="EN penalties: N1xN2 values of l1 x l2 (N2 <= 4)")
@@ -483,6 +532,9 @@ def _extra_kwargs(a) -> Dict:
         from .sorted_portfolios import parse_double_quantiles
         kw.update(double_sorts=a.double_sorts, double_quantiles=parse_double_quantiles(a.double_quantiles),
                   double_mode=a.double_mode, double_out=a.double_out, sort_split=a.sort_split)
+    if a.tree_sorts or a.tree_chars:
+        kw.update(tree_sorts=a.tree_sorts, tree_chars=a.tree_chars, tree_depth=a.tree_depth, tree_splits=a.tree_splits,
+                  tree_out=a.tree_out, sort_split=a.sort_split)
     if a.benchmarks:
         from .benchmarks import parse_grid
         kw.update(benchmarks=True, benchmark_grid=parse_grid(a.benchmark_grid), benchmark_center=a.benchmark_center,

@@ -46,8 +46,8 @@ Double sorts (``double_sort_numpy`` is the definition, ``Engine.double_sorted_po
   ``A == B`` is legal and gets no special case.
 
 Out of scope: value-weighted buckets (the panel carries no market cap; ``sort_buckets_numpy`` and
-the engine methods accept further value columns), triple sorts, plots (the beta network:
-``analysis.prediction``).
+the engine methods accept further value columns), plots (the beta network:
+``analysis.prediction``). Sorts on three or more keys: ``analysis.tree_sorts``.
 """
 from __future__ import annotations
 
