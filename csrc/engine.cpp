@@ -49,6 +49,7 @@
 #include "linport.h"
 #include "xgram.h"
 #include "xrank.h"
+#include "ximpute.h"
 #include "pred.h"
 #include "rnn.h"
 #include "update.h"
@@ -3729,6 +3730,28 @@ PYBIND11_MODULE(_dlap_hip, m) {
   m.def("rank_supported", [](int N) { return xrank_supported(N); });
   m.def("rank_block_keys", []() { return xrank_block_keys(); });
   m.attr("XRANK_MAX_N") = (int)XRANK_MAX_N;
+  m.def("characteristic_moments",
+        [](uintptr_t y, uintptr_t rowok, uintptr_t S, uintptr_t C, long long T, int N, int F, uintptr_t stream) {
+          launch_ximp_gram(reinterpret_cast<const float*>(y), reinterpret_cast<const uint8_t*>(rowok),
+                           reinterpret_cast<double*>(S), reinterpret_cast<int*>(C), T, N, F,
+                           reinterpret_cast<hipStream_t>(stream));
+        },
+        py::arg("y"), py::arg("rowok"), py::arg("S"), py::arg("C"), py::arg("T"), py::arg("N"), py::arg("F"),
+        py::arg("stream") = 0,
+        "masked second moments S (fp64) and pair counts C (int32) [T][F][F] of a dense fp32 chunk [T][N][F] (device pointers)");
+  m.def("xs_fill",
+        [](uintptr_t y, uintptr_t rowok, uintptr_t lam, uintptr_t out, long long T, int N, int F, int K, float gamma,
+           uintptr_t stream) {
+          launch_ximp_fill(reinterpret_cast<const float*>(y), reinterpret_cast<const uint8_t*>(rowok),
+                           reinterpret_cast<const float*>(lam), reinterpret_cast<float*>(out), T, N, F, K, gamma,
+                           reinterpret_cast<hipStream_t>(stream));
+        },
+        py::arg("y"), py::arg("rowok"), py::arg("lam"), py::arg("out"), py::arg("T"), py::arg("N"), py::arg("F"),
+        py::arg("K"), py::arg("gamma"), py::arg("stream") = 0,
+        "ridge fit on the loadings lam [T][F][K] and fill of the holes of a dense fp32 chunk (device pointers; out may be y)");
+  m.def("ximp_supported", [](int F, int K) { return ximp_supported(F, K); });
+  m.def("ximp_run", []() { return ximp_run(); });
+  m.attr("XIMP_MAX_K") = (int)XIMP_MAX_K;
   m.attr("HIST_W") = (int)HIST_W;
   m.attr("SC_NSCAL") = (int)SC_NSCAL;
 }
