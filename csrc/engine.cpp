@@ -1795,6 +1795,19 @@ class Engine {
     pack(g, false);
     h_valid_ = false;
   }
+  // (tests) the SDF keep words of one dropout-step parity half of model g's train split
+  py::array_t<uint32_t> keep_words(int g, int parity) {
+    ensure_jobs();
+    check_g(g);
+    if (parity < 0 || parity > 1) throw std::invalid_argument("parity must be 0 or 1");
+    const size_t half = (size_t)((splits_[0].R + 31) / 32) * md_.nl_s * 64;
+    sync();
+    py::array_t<uint32_t> out((py::ssize_t)half);
+    if (ws(g, 0).gb.n < 2 * half) throw std::runtime_error("keep_words: no keep words allocated for this split");
+    if (half)
+      HIP_LEGACY(hipMemcpy(out.mutable_data(), ws(g, 0).gb.p + (size_t)parity * half, half * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return out;
+  }
   // dropout stream position of model g (module API: fresh masks per forward), no host sync
   void set_drop_step(int g, int step) { launch_set_int(models_[check_g(g)].drop_step.p, step, st_); }
   // device-to-device copies of engine state into caller-owned device memory (stream-ordered)
@@ -2138,6 +2151,22 @@ class Engine {
       // inside a graph costs ~5-6 us on the chain and a graph that ends on two queues ~12 us at its
       // boundary (profiles/r5_*timeline*); these cost one poll each.
       p.split_graphs = k_.split_graphs && !safe_mode_ && p.adam_in_tail && (p.sep_eval || p.eval_in_fwd);
+      // The next step's dropout keep words from blocks of the tail launch (the split graphs with the
+      // dense-state tail: one LSTM layer of width 4): k_dropmask leaves the evaluation queue, whose
+      // bookkeeping signal the update waits for; the blocks hash beside the serial BPTT chain of the
+      // tail's block 0. One model per launch only (as the tail's one-wave build, tail_one_wave): a
+      // batched epoch is not bound by block 0, and with mask blocks it measured slower: 0.1896 ->
+      // 0.1949 ms per epoch at 2 models, 0.656 -> 0.721 at 9
+      // (profiles/fwd_bptt_tail_masks_bench.txt). Batched models keep k_dropmask on the evaluation
+      // queue unless DLAP_TAIL_MASKS > 1 forces that many mask blocks per model (tests, A/B runs).
+      // Blocks per model: at least 16 tiles each (one pass of a block's four waves), at most 224
+      // (most CUs of the device; 128 and 448 measured equal within noise, 64 and 896 slower).
+      p.tail_masks = k_.tail_masks != 0 && p.split_graphs && md_.dropout > 0.f && md_.H == 4 && md_.nrnn == 1 &&
+                     (G_ == 1 || k_.tail_masks > 1);
+      if (p.tail_masks) {
+        const int ntiles = (splits_[0].R + 31) / 32;
+        p.mask_blocks = k_.tail_masks > 1 ? std::min(k_.tail_masks, ntiles) : std::max(1, std::min((ntiles + 15) / 16, 224));
+      }
       // Phase 2: k_finalize -> k_wgrad -> k_adam and the train metrics as ONE launch (k_lstm_tail,
       // phase 2: the per-period sums relayed to the W_macro helpers, the moment network's clip + Adam
       // in the last blocks); the frozen SDF's LSTM recurrence once per run_epochs call
@@ -2197,6 +2226,9 @@ class Engine {
     d["adam_in_tail"] = m.tail_adam && plan_[1].eval_in_fwd;   // (of the eval-in-forward epoch)
     d["split_graphs"] = m.split;
     d["eval_sep"] = m.sep;
+    // the split graphs' tail launch writes the next step's keep words (and in how many blocks per model)
+    d["tail_masks"] = m.split && plan_[1].tail_masks;
+    d["tail_mask_blocks"] = m.split && plan_[1].tail_masks ? plan_[1].mask_blocks : 0;
     d["host_launch_us_per_epoch"] = host_launch_n_ ? 1e6 * host_launch_s_ / host_launch_n_ : 0.0;
     // backward launch shape: fine slabs per model (R-only partition), fine slabs per workgroup
     d["bwd_nfine"] = nfine_; d["bwd_fpw"] = fpw_;
@@ -3178,8 +3210,10 @@ class Engine {
     const LossJob* lm = tp.tail_metrics && phase != 2 ? loss_tab(phase, tp.gram) : nullptr;
     if (plan_[phase].tail_fused) {
       HTRACE("launch_lstm_tail");
+      const bool masks = tp.tail_masks && tp.tail_adam != 0;
       launch_lstm_tail(as<UpdJob>(j_upd_), as<FinJob>(j_fin_), G_, dd(), md_, D.T, slab_stride(), st_, lm,
-                       tp.tail_adam, tp.lr);
+                       tp.tail_adam, tp.lr, 1, masks ? as<MlpJob>(j_mlp_train_[phase]) : nullptr, md_.md.nl_sdf,
+                       masks ? plan_[phase].mask_blocks : 0);
       return;
     }
     if (lm) launch_job_metrics(lm, G_, st_);
@@ -3285,6 +3319,7 @@ class Engine {
     tp.premasked = true;
     tp.tail_metrics = true;
     tp.tail_adam = sep ? 3 : 2;
+    tp.tail_masks = plan_[phase].tail_masks;
     tp.eval_rnn = !sep;
     tp.esig = sep ? nullptr : esync_.p;
     enqueue_train_grads(tp);
@@ -3306,7 +3341,7 @@ class Engine {
       launch_wait_count(esync_.p, ne_per_model() * G_, k_.spin_limit, prog_.p, G_, st2_);
     }
     enqueue_eval_towers(st2_, ep);
-    enqueue_dropmask(phase, 1, st2_);
+    if (!plan_[phase].tail_masks) enqueue_dropmask(phase, 1, st2_);   // (else: the chain's tail launch)
     enqueue_epoch_end(phase, ignore_epoch, sel, st2_, 1);
   }
   // One-graph pipelined epoch (the split graphs' fallback: DLAP_SPLIT_GRAPHS=0, the update outside
@@ -3698,6 +3733,7 @@ PYBIND11_MODULE(_dlap_hip, m) {
       .def("split_rows", &Engine::split_rows)
       .def("join_to", &Engine::join_to)
       .def("set_drop_step", &Engine::set_drop_step)
+      .def("keep_words", &Engine::keep_words)
       .def("copy_ws", &Engine::copy_ws)
       .def("copy_grads", &Engine::copy_grads)
       .def("copy_hidden", &Engine::copy_hidden)

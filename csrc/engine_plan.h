@@ -42,6 +42,9 @@ struct Knobs {
   int gram_plan;           // DLAP_GRAM_PLAN (1): per-phase cost model; 0 Gram wherever it applies,
                            //   2 dense evaluation splits, 3 dense train split
   bool fused_pack;         // DLAP_FUSED_PACK (1): k_adam re-packs through per-parameter scatter lists
+  int tail_masks;          // DLAP_TAIL_MASKS (1): split graphs of one model, the next step's keep words from
+                           //   blocks of the tail launch instead of k_dropmask on the evaluation queue (> 1:
+                           //   that many mask blocks per model at any batch size, for tests and measurements)
   // ---- in-kernel waits, co-residency
   int prog_mode;           // DLAP_PROG_MODE (1): see MlpJob::prog_mode
   unsigned spin_limit;     // DLAP_PROG_SPIN_LIMIT (1 << 22): polls before a wait gives up (safe mode raises
@@ -83,6 +86,7 @@ inline Knobs read_knobs(int G, bool fp32) {
   k.gram = env_int("DLAP_GRAM", 1) != 0;
   k.gram_plan = env_int("DLAP_GRAM_PLAN", 1);
   k.fused_pack = env_int("DLAP_FUSED_PACK", 1) != 0;
+  k.tail_masks = std::max(0, env_int("DLAP_TAIL_MASKS", 1));
   k.prog_mode = env_int("DLAP_PROG_MODE", 1);
   k.spin_limit = (unsigned)env_int("DLAP_PROG_SPIN_LIMIT", 1 << 22);
   k.fused_cap = env_int("DLAP_FUSED_CAP", -1);
@@ -127,6 +131,8 @@ struct PhasePlan {
   bool tail_fused = false;      // backward tail as one launch (k_lstm_tail)
   bool adam_in_tail = false;    // the tail may carry the clip + Adam update (co-residency guard passed)
   bool split_graphs = false;    // training chain and evaluation as two graphs
+  bool tail_masks = false;      // ... whose tail launch hashes the next step's keep words (no k_dropmask on
+  int mask_blocks = 0;          //     the evaluation queue), in this many more blocks per model
   bool mom_tail = false;        // phase 2: the moment network's one-launch tail
   bool p2_lstm_cached = false;  // phase 2: the LSTM recurrence once per run
   bool eval_fusable = false;    // an evaluation on its own may run the fused LSTM + tower launch ...
@@ -161,6 +167,7 @@ struct TrainPass {
   bool defer_metrics = false;   // the caller runs the train metrics (EV_MID is recorded after the loss pass)
   bool tail_metrics = false;    // the train metrics run in the backward tail
   int tail_adam = 0;            // the update runs in the fused tail (launch_lstm_tail's adam mode), 0: not
+  bool tail_masks = false;      // ... and the tail's mask blocks write the next step's keep words
   bool mom_adam = false;        // phase 2: metrics + Adam in the moment network's tail launch
 };
 

@@ -35,6 +35,7 @@
 #include "mlp.h"
 #include "lstm_gls.h"
 #include "tower_dev.h"
+#include "dropmask_dev.h"
 
 // Waves per SIMD the forward tower kernel is compiled for (its VGPR budget = 512 / this).
 #ifndef DLAP_FWD_WPS
@@ -1146,21 +1147,11 @@ __global__ __launch_bounds__(256) void k_dropmask(const MlpJob* __restrict__ job
   const MlpJob& J = jobs[blockIdx.y];
   const int ntiles = (J.R + 31) >> 5;
   const int gid = blockIdx.x * 256 + threadIdx.x;
-  const int tile = gid >> 6, lane = gid & 63, q = lane >> 4;
+  const int tile = gid >> 6, lane = gid & 63;
   if (tile >= ntiles) return;
   const uint32_t step = (J.step ? (uint32_t)*gp(J.step) : 0u) + (uint32_t)step_offset;
   if (!(J.dropout > 0.f)) return;        // (no keep words: this model's towers do not read them)
-  const uint32_t thr16 = (uint32_t)(J.dropout * 65536.f + 0.5f);
-  uint32_t rowmix[2];
-#pragma unroll
-  for (int b = 0; b < 2; ++b) {
-    const int r = tile * 32 + 16 * b + (lane & 15);
-    const int2 ti = gp(J.rowti)[min(r, J.R - 1)];
-    // rows beyond R hash as dense row -1, as the towers do (their words are never used)
-    rowmix[b] = row_mix(r < J.R ? (uint32_t)(ti.x * J.N + ti.y) : 0xFFFFFFFFu);
-  }
-  const auto dst = gp(const_cast<uint32_t*>(J.gbits)) + (size_t)(step & 1u) * J.gb_half + (size_t)tile * D.nl_sdf * 64 + lane;
-  for (int j = 0; j < D.nl_sdf; ++j) dst[64 * j] = keep_word<4>(dropout_key(J.seed, step, j), rowmix, thr16, q);
+  dropmask_tiles<1>(J, D.nl_sdf, step, tile, 1, ntiles, lane);
 }
 
 void launch_dropmask(const MlpJob* jobs, int njobs, int ntiles, const MlpDims& D, int step_offset,

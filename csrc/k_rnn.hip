@@ -29,6 +29,7 @@
 #include "finalize.h"
 #include "loss_dev.h"
 #include "pack_dev.h"
+#include "dropmask_dev.h"
 
 #define DLAP_MAX_M 1024
 
@@ -1246,6 +1247,14 @@ DLAP_DEV void tail_adam(const UpdJob& U, const ModelDesc* __restrict__ md, float
 // pipelined epoch needs no fork to the evaluation branch for them.
 // adam (tail_adam): the clip + Adam update of the step in the launch's last blocks (2: after
 // the evaluation branch's signal; the only mode).
+// mjobs / nmask (adam launches, PhasePlan::tail_masks): nmask more blocks per model, the highest
+// block numbers, hash the SDF keep words of dropout step drop_step + 1 into that step's parity half
+// (dropmask_tiles, k_dropmask's body: the same words at the same addresses), each a contiguous
+// range of tiles. That half was last read by the previous epoch's forward and backward, finished
+// in stream order; the end of the launch orders the words before the next forward. The blocks wait
+// for nothing and arrive like every other block, so the Adam blocks -- and with them the advance
+// of drop_step, read by every block before it arrives -- wait for the masks: the launch still need
+// not be resident at once.
 // WPS (waves per SIMD the register budget is set for): 2 keeps two workgroups on a CU, but at
 // LSTM width 4 the dense-state BPTT of block 0 then spills (432 bytes of scratch per thread, on
 // the serial path: BPTT 18.5 -> 16.5 us without). One model per launch has under 400 workgroups
@@ -1255,7 +1264,8 @@ DLAP_DEV void tail_adam(const UpdJob& U, const ModelDesc* __restrict__ md, float
 template <int HM, int WPS>
 __global__ __launch_bounds__(256, WPS) void k_lstm_tail(const UpdJob* __restrict__ ujobs, const FinJob* __restrict__ fjobs,
                                                    const ModelDesc* __restrict__ md, int slab_stride, int nslab_blocks,
-                                                   const LossJob* __restrict__ ljobs, int adam, float lr, int phase) {
+                                                   const LossJob* __restrict__ ljobs, int adam, float lr, int phase,
+                                                   const MlpJob* __restrict__ mjobs, int nl_sdf, int nmask) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const UpdJob& U = ujobs[blockIdx.y];
   const FinJob& F = fjobs[blockIdx.y];
@@ -1295,8 +1305,27 @@ __global__ __launch_bounds__(256, WPS) void k_lstm_tail(const UpdJob* __restrict
     finalize_block(F, md, phase, slab_stride, nslab_blocks + b, U.tail_ctr + TAIL_CNT);
   } else if (b < U.T + nslab_blocks) {
     finalize_block(F, md, phase, slab_stride, b - U.T);
-  } else if (b >= U.T + nslab_blocks + nwg) {      // the train split's job metrics
-    if (ljobs) job_metrics_body<256>(ljobs[blockIdx.y], sm + DLAP_MAX_T, sm);
+  } else if (b >= U.T + nslab_blocks + nwg) {
+    const int mb = b - (U.T + nslab_blocks + nwg) - (ljobs ? 1 : 0);
+    if (mb < 0) {                                    // the train split's job metrics
+      job_metrics_body<256>(ljobs[blockIdx.y], sm + DLAP_MAX_T, sm);
+    } else if (mjobs) {
+      // mask block mb of nmask (adam launches only): the keep words of the NEXT dropout step for a
+      // contiguous range of tiles, k_dropmask's body. It waits for nothing; the step counter it
+      // reads is advanced only after every block of the launch, this one included, has arrived
+      const MlpJob& MJ = mjobs[blockIdx.y];
+      __syncthreads();                               // s_steps
+      RNN_TS(21, blockIdx.y == 0 && mb == 0);
+      if (MJ.dropout > 0.f) {
+        const int ntiles = (MJ.R + 31) >> 5, per = (ntiles + nmask - 1) / nmask;
+        const int lo = mb * per, hi = min(lo + per, ntiles);
+        const uint32_t step = (uint32_t)s_steps[1] + 1u;
+        constexpr int MU = 4;                        // tiles per wave and pass (loads batched)
+        for (int t0 = lo + (int)(threadIdx.x >> 6); t0 < hi; t0 += 4 * MU)
+          dropmask_tiles<MU>(MJ, nl_sdf, step, t0, 4, hi, threadIdx.x & 63);
+      }
+      RNN_TS(22, blockIdx.y == 0 && mb == nmask - 1);
+    }
   } else {
     // W_ih helper: k_wgrad's block, its macro operands requested first, then the wait for the
     // gate gradients (relaxed poll, one agent acquire, barrier) before their loads
@@ -1343,7 +1372,8 @@ bool lstm_tail_supported(const ModelDesc& mh, int T) {
   if (tail_dense(mh) && scan_env && std::atoi(scan_env) == 0) return false;
   // (+ static LDS) two per CU for the dense map; one per CU otherwise (H = 8: ~100 KB at T = 240).
   // Residency is not required: the only in-kernel waits are on lower-numbered blocks (the LSTM
-  // block waits for the period blocks dispatched right after it) or, for Adam, the last arrivals
+  // block waits for the period blocks dispatched right after it) or, for Adam, the last arrivals;
+  // the mask blocks (tail_masks) never wait
   const size_t lim = tail_dense(mh) ? 80 * 1024 : 160 * 1024;
   return lstm_tail_lds_bytes(mh, T) + 6400 <= lim;
 }
@@ -1370,20 +1400,23 @@ int lstm_tail_capacity(const ModelDesc& mh, int T, int njobs) {
   return per_cu * ncu;
 }
 void launch_lstm_tail(const UpdJob* ujobs, const FinJob* fjobs, int njobs, const ModelDesc* md, const ModelDesc& mh,
-                      int T, int slab_stride, hipStream_t st, const LossJob* ljobs, int adam, float lr, int phase) {
+                      int T, int slab_stride, hipStream_t st, const LossJob* ljobs, int adam, float lr, int phase,
+                      const MlpJob* mjobs, int nl_sdf, int nmask) {
+  if (!mjobs || !adam || phase == 2 || nmask < 0) nmask = 0;   // (the mask blocks read the tail's step record)
+  if (nmask == 0) mjobs = nullptr;
   const int nslab_blocks = (phase == 2 ? mh.ntile_m : mh.ntile_s) * 64 + (SLAB_EXTRA + 63) / 64;
   const int nwg = (mh.M + 1 + 15) / 16;
   const size_t sh = tail_dyn_lds(mh, T, phase);
-  const dim3 grid(1 + T + nslab_blocks + nwg + (ljobs ? 1 : 0), njobs);
+  const dim3 grid(1 + T + nslab_blocks + nwg + (ljobs ? 1 : 0) + nmask, njobs);
   if (tail_one_wave(mh, njobs))
     hipLaunchKernelGGL((k_lstm_tail<4, 1>), grid, dim3(256), sh, st, ujobs, fjobs, md, slab_stride, nslab_blocks, ljobs, adam,
-                       lr, phase);
+                       lr, phase, mjobs, nl_sdf, nmask);
   else if (mh.H <= 4)
     hipLaunchKernelGGL((k_lstm_tail<4, 2>), grid, dim3(256), sh, st, ujobs, fjobs, md, slab_stride, nslab_blocks, ljobs, adam,
-                       lr, phase);
+                       lr, phase, mjobs, nl_sdf, nmask);
   else
     hipLaunchKernelGGL((k_lstm_tail<8, 2>), grid, dim3(256), sh, st, ujobs, fjobs, md, slab_stride, nslab_blocks, ljobs, adam,
-                       lr, phase);
+                       lr, phase, mjobs, nl_sdf, nmask);
   HIP_OK(hipGetLastError());
 }
 

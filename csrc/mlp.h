@@ -25,7 +25,8 @@ struct MlpJob {
   float* v_out;           // bwd mom: [R][64] dL/d(moment layer-0 pre-activation) per row
   const uint32_t* gbits;  // SDF dropout keep words (split layout, common.h), two halves by
                           //   dropout-step parity: [parity][tile][layer][lane]. k_dropmask
-                          //   writes them; the train forward and the backward (which recomputes
+                          //   (or the tail launch's mask blocks: dropmask_dev.h) writes them;
+                          //   the train forward and the backward (which recomputes
                           //   the forward) read the half of their step. Moment-tower masks are
                           //   hashed in the kernels (keep_word).
   int gb_half;            // words per parity half (ntiles * nl_sdf * 64)

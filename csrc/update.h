@@ -123,9 +123,14 @@ struct LossJob;
 // the launch's last Adam block advances the model's update generation (k_wait_gen, DLAP_EVAL_SEP)
 // phase 2: the moment network's tail -- k_finalize + k_wgrad (the macro columns of moment layer
 // 0) [+ k_adam]; block 0 relays the per-period sums' count to the W_macro helpers (no BPTT)
+// mjobs, nl_sdf, nmask (adam launches of phases 1 / 3 only, else ignored): nmask more blocks per
+// model, after the metrics block, hash the SDF keep words of the NEXT dropout step (drop_step + 1,
+// k_dropmask's body and addresses; mjobs = the step's training tower jobs) -- they wait for
+// nothing and arrive like every other block, so the update's advance of drop_step follows them
+struct MlpJob;
 void launch_lstm_tail(const UpdJob* ujobs, const FinJob* fjobs, int njobs, const ModelDesc* md, const ModelDesc& mh,
                       int T, int slab_stride, hipStream_t st, const LossJob* ljobs = nullptr, int adam = 0,
-                      float lr = 0.f, int phase = 1);
+                      float lr = 0.f, int phase = 1, const MlpJob* mjobs = nullptr, int nl_sdf = 0, int nmask = 0);
 // whether the phase-2 tail applies (macro columns in moment layer 0)
 bool mom_tail_supported(const ModelDesc& mh, int T);
 void launch_pack(float* const* params_unused, const UpdJob* jobs, int njobs, const ModelDesc* md,

@@ -5,7 +5,9 @@ the evaluation graph beside it, whose k_epoch_end signals the tail's update.
 Prints, over the body epochs inside an unrolled graph (epochs longer than --steady us are launch
 gaps, heads or phase changes and are left out): the time from the end of k_tbwd_sdf to the end of
 k_epoch_end, from there to the end of k_lstm_tail, the chain's kernel durations, k_dropmask on
-the evaluation queue -- then one epoch, kernel by kernel, in us from the end of its fused forward.
+the evaluation queue (n = 0 where the tail launch hashes the keep words, DLAP_TAIL_MASKS; the mask
+blocks' in-kernel stamps are printed by tools/lstm_timing.py) -- then one epoch, kernel by kernel,
+in us from the end of its fused forward.
 
 Usage: python tools/epoch_paths.py <prof dir> [--epochs 45] > profiles/<name>.txt
 """

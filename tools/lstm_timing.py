@@ -43,6 +43,11 @@ def main():
         if eng.eng.fused_info().get("adam_in_tail") and pipe and ts[20] > ts[18]:
             print(f"    tail Adam    : last arrival {us(10, 18):7.1f} after the gates  Adam block 0 released "
                   f"{us(18, 19):7.1f}  update done {us(19, 20):7.1f} later")
+        if eng.eng.fused_info().get("tail_masks") and pipe and ts[22] > ts[21] > ts[8]:
+            # the tail's mask blocks (next step's keep words): first block started / last block done,
+            # from the start of block 0, against block 0's gates and the last arrival
+            print(f"    tail masks   : {eng.eng.fused_info()['tail_mask_blocks']} blocks  first start {us(8, 21):7.1f}  "
+                  f"last done {us(8, 22):7.1f}  (gates done {us(8, 10):7.1f}  last arrival {us(8, 18):7.1f}) from block 0's start")
         print(f"  k_proj tile0   : total {us(12, 14):7.1f}")
         m = np.array(mod.Engine.mlp_timestamps(), dtype=np.int64)
         um = lambda a, b: (m[b] - m[a]) / 100.0  # noqa: E731
