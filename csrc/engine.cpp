@@ -50,6 +50,7 @@
 #include "xgram.h"
 #include "xrank.h"
 #include "ximpute.h"
+#include "encd.h"
 #include "pred.h"
 #include "rnn.h"
 #include "update.h"
@@ -3788,6 +3789,36 @@ PYBIND11_MODULE(_dlap_hip, m) {
   m.def("ximp_supported", [](int F, int K) { return ximp_supported(F, K); });
   m.def("ximp_run", []() { return ximp_run(); });
   m.attr("XIMP_MAX_K") = (int)XIMP_MAX_K;
+  m.def("en_paths",
+        [](uintptr_t A, uintptr_t a_of, uintptr_t b, uintptr_t l1s, uintptr_t l2, uintptr_t theta, uintptr_t sweeps,
+           uintptr_t nnz, uintptr_t state, int NA, long long P, int n, int n1, int max_sweeps, int max_assets,
+           int sweeps_per_launch, uintptr_t stream) {
+          std::vector<float> ms;
+          std::vector<int> updates;
+          const int launches =
+              encd_run(reinterpret_cast<const double*>(A), reinterpret_cast<const int*>(a_of),
+                       reinterpret_cast<const double*>(b), reinterpret_cast<const double*>(l1s),
+                       reinterpret_cast<const double*>(l2), reinterpret_cast<double*>(theta),
+                       reinterpret_cast<int*>(sweeps), reinterpret_cast<int*>(nnz), reinterpret_cast<void*>(state), NA, P, n,
+                       n1, max_sweeps, max_assets, sweeps_per_launch, reinterpret_cast<hipStream_t>(stream), &ms, &updates);
+          py::dict r;
+          r["launches"] = launches;
+          r["launch_ms"] = ms;
+          r["updates"] = updates;
+          return r;
+        },
+        py::arg("A"), py::arg("a_of"), py::arg("b"), py::arg("l1s"), py::arg("l2"), py::arg("theta"), py::arg("sweeps"),
+        py::arg("nnz"), py::arg("state"), py::arg("NA"), py::arg("P"), py::arg("n"), py::arg("n1"), py::arg("max_sweeps"),
+        py::arg("max_assets") = -1, py::arg("sweeps_per_launch") = (int)ENCD_DEFAULT_SWEEPS_PER_LAUNCH, py::arg("stream") = 0,
+        "elastic-net coordinate-descent paths: A [NA][n][n], b [P][n], l1s [P][n1], l2 [P] fp64, a_of [P] int32 -> theta "
+        "[P][n1][n] fp64, sweeps / nnz [P][n1] int32; state: encd_state_bytes(P, n) (device pointers; returns the launches, "
+        "their device times and the updates per path)");
+  m.def("encd_supported", [](int n) { return encd_supported(n); });
+  m.def("encd_state_bytes", [](long long P, int n) { return encd_state_bytes(P, n); });
+  m.def("encd_threads", []() { return encd_threads(); });
+  m.def("encd_prefetch", []() { return encd_prefetch(); });
+  m.attr("ENCD_MAX_N") = (int)ENCD_MAX_N;
+  m.attr("ENCD_DEFAULT_SWEEPS_PER_LAUNCH") = (int)ENCD_DEFAULT_SWEEPS_PER_LAUNCH;
   m.attr("HIST_W") = (int)HIST_W;
   m.attr("SC_NSCAL") = (int)SC_NSCAL;
 }

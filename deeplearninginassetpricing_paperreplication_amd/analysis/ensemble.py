@@ -103,7 +103,8 @@ def evaluate_ensemble(checkpoint_dirs: Sequence[str], data_dir: str, device: str
                       knockout_base="zero", knockout_xs_r2: bool = False, knockout_out: str = None,
                       knockout_macro: bool = False, knockout_macro_groups=None, knockout_macro_base="zero",
                       tree_sorts=None, tree_chars=None, tree_depth: int = 3, tree_splits=2,
-                      tree_out: str = None) -> Dict:
+                      tree_out: str = None, tree_prune: bool = False, prune_max_assets: int = 40,
+                      prune_grid="3x3x16", prune_out: str = None) -> Dict:
     """Reference output and return value; ``paper=True`` (CLI ``--paper_metrics``) adds the
     paper's EV / XS-R² / turnover / max 1-month loss of the ensemble's SDF factor per split;
     ``importance=True`` (CLI ``--variable_importance``) adds the sensitivity ranking of the
@@ -159,9 +160,16 @@ def evaluate_ensemble(checkpoint_dirs: Sequence[str], data_dir: str, device: str
     --tree_depth D``: every ordered sequence of ``D`` of these keys, the asset-pricing-tree set) add the
     tree-sorted portfolios of ``sort_split`` (``analysis.tree_sorts``; ``tree_splits``: one integer for
     every level or ``2x3x3``, at most 36 leaves and 4096 trees), priced by the SDF, under the key
-    ``tree_sorts`` and write them to ``tree_out`` (JSON) when given."""
+    ``tree_sorts`` and write them to ``tree_out`` (JSON) when given.
+    ``tree_prune=True`` (CLI ``--tree_prune``, with ``tree_sorts`` or ``tree_chars``) sorts the same trees
+    on all three splits and prunes their nodes into a sparse mean-variance SDF (``analysis.tree_prune``:
+    at most ``prune_max_assets`` nodes, ``prune_grid`` = ``N0xN2xN1`` penalties of ``l0 x l2 x l1``,
+    selected on the validation split), printed next to the ensemble under the key ``tree_prune`` and
+    written to ``prune_out`` (JSON) when given."""
     say = print if verbose else (lambda *a, **k: None)
     bar = "=" * 70
+    if tree_prune and not (tree_sorts or tree_chars):
+        raise ValueError("tree_prune needs tree_sorts or tree_chars (CLI: --tree_prune with --tree_sorts / --tree_chars)")
     say(bar); say(f"ENSEMBLE EVALUATION ({len(checkpoint_dirs)} models, averaged weights)"); say(bar); say()
     datasets = load_splits(data_dir)
     batches = {s: d.get_full_batch() for s, d in zip(SPLITS, datasets)}
@@ -320,6 +328,34 @@ def evaluate_ensemble(checkpoint_dirs: Sequence[str], data_dir: str, device: str
             with open(tree_out, "w") as fh:
                 json.dump(ts.tree_to_json(res_ts, priced), fh, indent=1)
             say(f"  Saved: {tree_out}"); say()
+        if tree_prune:
+            from . import tree_prune as tp
+            n0, n2, n1 = tp.parse_prune_grid(prune_grid)
+            by_split = {sort_split: res_ts}
+            for s in SPLITS:
+                if s in by_split:
+                    continue
+                if str(device).startswith("cuda"):
+                    ws = average_weights(list(wdev[s].cpu().numpy()), np_batches[s]["mask"])
+                else:
+                    ws = average_weights([w[s] for w in weights], np_batches[s]["mask"])
+                by_split[s] = ts.tree_sorted_portfolios(models, batches[s], trees, splits=splits, device=device, names=names,
+                                                        weights=ws)
+            pruned = tp.prune_trees(by_split, l0=tp.PRUNE_L0[:n0], l2_rel=tp.PRUNE_L2_REL[:n2], n1=n1,
+                                    max_assets=prune_max_assets, device=device)
+            out["tree_prune"] = pruned
+            F = int(b["individual_features"].shape[2])
+            kn = ([str(x) for x in names] if names is not None and len(names) == F else [str(j) for j in range(F)]) + ["weight"]
+            say(bar); say(f"PRUNED TREES (elastic-net mean-variance SDF on the tree nodes, at most {int(prune_max_assets)})")
+            say(bar); say()
+            for line in tp.format_pruned(pruned, gan={k: res[k] for k in ("train_sharpe", "valid_sharpe", "test_sharpe")},
+                                         key_names=kn):
+                say(line)
+            say()
+            if prune_out:
+                with open(prune_out, "w") as fh:
+                    json.dump(tp.pruned_to_json(pruned), fh, indent=1)
+                say(f"  Saved: {prune_out}"); say()
     pred_json = {}
     if benchmark_ffn and not benchmarks:
         raise ValueError("benchmark_ffn needs benchmarks (CLI: --benchmark_ffn with --benchmarks)")
@@ -481,6 +517,11 @@ def _parser():
     p.add_argument("--tree_splits", type=str, default="2",
                    help="children per node: one integer for every level, or Q1xQ2x.. (2..16 each, at most 36 leaves)")
     p.add_argument("--tree_out", type=str, default=None, help="write the tree-sorted results to FILE.json")
+    p.add_argument("--tree_prune", action="store_true",
+                   help="with --tree_sorts / --tree_chars: prune the tree nodes into a sparse mean-variance SDF (elastic net)")
+    p.add_argument("--prune_max_assets", type=int, default=40, help="nodes of the pruned SDF at most")
+    p.add_argument("--prune_grid", type=str, default="3x3x16", help="penalties N0xN2xN1 of l0 (<= 3) x l2 (<= 3) x l1")
+    p.add_argument("--prune_out", type=str, default=None, help="write the pruning results to FILE.json")
     p.add_argument("--benchmarks", action="store_true",
                    help="also evaluate the linear (LS) and elastic-net (EN) benchmark SDFs next to the ensemble")
     p.add_argument("--benchmark_grid", type=str, default="16x4", help="EN penalties: N1xN2 values of l1 x l2 (N2 <= 4)")
@@ -535,6 +576,10 @@ def _extra_kwargs(a) -> Dict:
     if a.tree_sorts or a.tree_chars:
         kw.update(tree_sorts=a.tree_sorts, tree_chars=a.tree_chars, tree_depth=a.tree_depth, tree_splits=a.tree_splits,
                   tree_out=a.tree_out, sort_split=a.sort_split)
+    if a.tree_prune:
+        if not (a.tree_sorts or a.tree_chars):
+            raise SystemExit("--tree_prune needs --tree_sorts or --tree_chars")
+        kw.update(tree_prune=True, prune_max_assets=a.prune_max_assets, prune_grid=a.prune_grid, prune_out=a.prune_out)
     if a.benchmarks:
         from .benchmarks import parse_grid
         kw.update(benchmarks=True, benchmark_grid=parse_grid(a.benchmark_grid), benchmark_center=a.benchmark_center,

@@ -25,8 +25,8 @@ Layout, level order (``tree_layout``): ``off[l] = n_0 + .. + n_{l-1}``, node ``(
 Per (period, tree, node) the raw result holds the row count and the float64 sums of the value
 columns (the return, then the ensemble weight); per (period, tree) ``breaks`` [NB].
 
-Out of scope: pruning the trees into an SDF (the elastic-net mean-variance step of the tree paper),
-sharing selects between trees with a common prefix, an independent (non-nested) mode, value
+Pruning the nodes into an SDF (the elastic-net mean-variance step of the tree paper) is
+``analysis.tree_prune``. Out of scope: sharing selects between trees with a common prefix, an independent (non-nested) mode, value
 weighting beyond a caller's value column, more than 36 leaves, plots.
 """
 from __future__ import annotations

@@ -74,7 +74,9 @@ def variant_path(variant: str) -> Path:
 # the default (3954/3999 vs 3990/3972 model-epochs/s, profiles/README.md).
 # k_tbwd.hip: the builtin MFMAs in VGPR form (the forward / chain layer results feed VALU work
 # without accumulator-file moves); its long-lived weight-gradient sums are pinned to AGPRs by asm.
-FILE_FLAGS: dict = {"k_tbwd.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
+# k_encd.hip: bit-exact fp64 against the numpy definition, so no multiply-add is contracted into an fma
+# (__dmul_rn / __dadd_rn and a file-scope pragma do not stop hipcc's default contraction, the flag does).
+FILE_FLAGS: dict = {"k_tbwd.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "k_encd.hip": ["-ffp-contract=off"]}
 
 
 def build(force: bool = False, jobs: int = 8, verbose: bool = True, ubsan: bool = False,
