@@ -46,6 +46,7 @@
 #include "qsort.h"
 #include "qsort2.h"
 #include "qtree.h"
+#include "qtree_weight.h"
 #include "linport.h"
 #include "xgram.h"
 #include "xrank.h"
@@ -1069,6 +1070,101 @@ class Engine {
     d["level_offsets"] = std::vector<int>(off, off + Dp + 2);
     d["break_offsets"] = std::vector<int>(boff, boff + Dp + 1);
     d["rows"] = D.R; d["gpu_ms"] = ms;
+    return d;
+  }
+  // Stock-level weights of a combination of tree nodes of split s (k_qtree_weight.hip, definition in
+  // qtree_weight.h): trees, splits, extra_keys as for tree_sorted_portfolios; breaks fp32 [T][P][NB]
+  // and count int32 [T][P][NN] of a tree sort of the same keys, coef fp64 [P][NN] (finite). w_out a
+  // dense device buffer [T][N] fp32, acc_out one of fp64 or 0: written at the valid (t, i) on the
+  // engine stream, every other element is left as it is. trees_per_pass: 0 for the default, else
+  // 1 .. QTREE_WEIGHT_MAX_TPP (no output bit depends on it). verify_inputs (a test knob) reads the
+  // device copies of breaks, count and coef back after the launch and returns inputs_unchanged.
+  // Reads the panel only. Returns gpu_ms,
+  // active_trees (those with a non-zero coefficient), passes, keys (distinct key columns of the
+  // active levels), segments and rows. An empty split or an all-zero coef launches nothing.
+  py::dict tree_weights(int s, std::vector<std::vector<int>> trees, std::vector<int> splits,
+                        py::array_t<float, py::array::c_style | py::array::forcecast> breaks,
+                        py::array_t<int, py::array::c_style | py::array::forcecast> count,
+                        py::array_t<double, py::array::c_style | py::array::forcecast> coef, uintptr_t extra_keys,
+                        int n_extra, uintptr_t w_out, uintptr_t acc_out, int trees_per_pass, bool verify_inputs) {
+    check_split(s, "tree_weights", kSplitIndex);
+    const int Dp = (int)splits.size();
+    if (Dp < 1 || Dp > QTREE_MAX_D) throw std::invalid_argument("tree_weights: splits must have 1 to 5 levels");
+    for (int q : splits)
+      if (q < 2 || q > QTREE_MAX_Q) throw std::invalid_argument("tree_weights: every split must be in [2, 16]");
+    int off[QTREE_MAX_D + 2], boff[QTREE_MAX_D + 1];
+    if (!qtree_layout(splits.data(), Dp, off, boff))
+      throw std::invalid_argument("tree_weights: the product of the splits must be at most 36");
+    if (n_extra < 0 || (n_extra > 0 && !extra_keys)) throw std::invalid_argument("tree_weights: n_extra needs extra_keys");
+    if (!w_out) throw std::invalid_argument("tree_weights: w_out is needed");
+    if (trees_per_pass < 0 || trees_per_pass > QTREE_WEIGHT_MAX_TPP)
+      throw std::invalid_argument("tree_weights: trees_per_pass must be in [0, 32]");
+    if ((int)trees.size() > QTREE_WEIGHT_MAX_TREES) throw std::invalid_argument("tree_weights: at most 4096 trees per call");
+    for (const auto& tr : trees) {
+      if ((int)tr.size() != Dp) throw std::invalid_argument("tree_weights: every tree needs one key per level of splits");
+      for (int c : tr)
+        if (c < 0 || c >= md_.F + n_extra) throw std::invalid_argument("tree_weights: key index outside [0, F + n_extra)");
+    }
+    const SplitDev& D = check_split(s, "tree_weights", kSplitSet | kSplitPeriods);
+    const int P = (int)trees.size(), NN = off[Dp + 1], NB = boff[Dp];
+    if (breaks.ndim() != 3 || breaks.shape(0) != D.T || breaks.shape(1) != P || breaks.shape(2) != NB)
+      throw std::invalid_argument("tree_weights: breaks must be [T][P][NB]");
+    if (count.ndim() != 3 || count.shape(0) != D.T || count.shape(1) != P || count.shape(2) != NN)
+      throw std::invalid_argument("tree_weights: count must be [T][P][NN]");
+    if (coef.ndim() != 2 || coef.shape(0) != P || coef.shape(1) != NN)
+      throw std::invalid_argument("tree_weights: coef must be [P][NN]");
+    for (ssize_t k = 0; k < coef.size(); ++k)
+      if (!std::isfinite(coef.data()[k])) throw std::invalid_argument("tree_weights: coef must be finite");
+    std::vector<int> flat, meta, ucols;
+    for (const auto& tr : trees) flat.insert(flat.end(), tr.begin(), tr.end());
+    const int Pa = P > 0 ? qtree_weight_plan(flat.data(), coef.data(), P, Dp, off, meta, ucols) : 0;
+    const int U = (int)ucols.size();
+    if (!qtree_weight_supported(splits.data(), Dp, P, D.T, U))
+      throw std::invalid_argument("tree_weights: not available for this call (T above 65535 or more than 32 distinct keys)");
+    const int tpp = trees_per_pass ? trees_per_pass : QTREE_WEIGHT_DEFAULT_TPP;
+    float ms = 0.f;
+    int nseg = 0;
+    bool inputs_same = true;
+    if (D.R > 0 && D.T > 0 && Pa > 0) {
+      std::vector<int> rp((size_t)D.T + 1), seg;
+      fetch(rp.data(), D.row_ptr.p, rp.size());
+      nseg = qtree_weight_segments(rp.data(), D.T, seg);
+      DevBuf<int> dseg, dmeta, dcols, dcnt;
+      DevBuf<float> dbrk;
+      DevBuf<double> dcoef;
+      up(dseg, seg.data(), seg.size());
+      up(dmeta, meta.data(), meta.size());
+      if (U > 0) up(dcols, ucols.data(), ucols.size());
+      up(dcnt, count.data(), (size_t)count.size());
+      up(dbrk, breaks.data(), (size_t)breaks.size());
+      up(dcoef, coef.data(), (size_t)coef.size());
+      QtreeWeightArgs A{};
+      A.pv = panel_view(D);
+      A.seg = reinterpret_cast<const int2*>(dseg.p); A.nseg = nseg;
+      A.Pa = Pa; A.meta = dmeta.p; A.U = U; A.ucols = dcols.p;
+      A.P = P; A.D = Dp;
+      for (int l = 0; l < Dp; ++l) A.Q[l] = splits[l];
+      A.E = n_extra; A.extra = reinterpret_cast<const float*>(extra_keys);
+      A.breaks = dbrk.p; A.count = dcnt.p; A.coef = dcoef.p;
+      A.tpp = tpp;
+      A.w_out = reinterpret_cast<float*>(w_out); A.acc_out = reinterpret_cast<double*>(acc_out);
+      ms = timed([&] { launch_qtree_weight(A, st_); });
+      if (verify_inputs) {                      // the device copies after the launch against what was uploaded
+        std::vector<float> hb((size_t)breaks.size());
+        std::vector<int> hc((size_t)count.size());
+        std::vector<double> hf((size_t)coef.size());
+        fetch(hb.data(), dbrk.p, hb.size());
+        fetch(hc.data(), dcnt.p, hc.size());
+        fetch(hf.data(), dcoef.p, hf.size());
+        inputs_same = std::memcmp(hb.data(), breaks.data(), hb.size() * sizeof(float)) == 0 &&
+                      std::memcmp(hc.data(), count.data(), hc.size() * sizeof(int)) == 0 &&
+                      std::memcmp(hf.data(), coef.data(), hf.size() * sizeof(double)) == 0;
+      }
+    }
+    py::dict d;
+    d["gpu_ms"] = ms; d["active_trees"] = Pa; d["passes"] = nseg > 0 && Pa > 0 ? (Pa + tpp - 1) / tpp : 0;
+    if (verify_inputs) d["inputs_unchanged"] = inputs_same;
+    d["keys"] = U; d["segments"] = nseg; d["rows"] = D.R;
     return d;
   }
   // Linear benchmark SDFs of split s (k_linport.hip, definitions in linport.h and
@@ -3697,6 +3793,9 @@ PYBIND11_MODULE(_dlap_hip, m) {
       .def("tree_sorted_portfolios", &Engine::tree_sorted_portfolios, py::arg("s"), py::arg("trees"),
            py::arg("splits"), py::arg("extra_keys") = 0, py::arg("n_extra") = 0, py::arg("values") = 0,
            py::arg("n_values") = 0)
+      .def("tree_weights", &Engine::tree_weights, py::arg("s"), py::arg("trees"), py::arg("splits"), py::arg("breaks"),
+           py::arg("count"), py::arg("coef"), py::arg("extra_keys") = 0, py::arg("n_extra") = 0, py::arg("w_out") = 0,
+           py::arg("acc_out") = 0, py::arg("trees_per_pass") = 0, py::arg("verify_inputs") = false)
       .def("managed_portfolios", &Engine::managed_portfolios, py::arg("s"))
       .def("linear_portfolios", &Engine::linear_portfolios, py::arg("s"), py::arg("theta"),
            py::arg("center") = py::none(), py::arg("w_out") = 0)
@@ -3819,6 +3918,20 @@ PYBIND11_MODULE(_dlap_hip, m) {
   m.def("encd_prefetch", []() { return encd_prefetch(); });
   m.attr("ENCD_MAX_N") = (int)ENCD_MAX_N;
   m.attr("ENCD_DEFAULT_SWEEPS_PER_LAUNCH") = (int)ENCD_DEFAULT_SWEEPS_PER_LAUNCH;
+  m.def("qtree_weight_supported",
+        [](std::vector<int> splits, int P, int T, int n_keys) {
+          return qtree_weight_supported(splits.data(), (int)splits.size(), P, T, n_keys);
+        },
+        py::arg("splits"), py::arg("P"), py::arg("T"), py::arg("n_keys"));
+  m.def("qtree_weight_lds_bytes", [](int tpp, int NN, int NB, int n_keys) { return qtree_weight_lds_bytes(tpp, NN, NB, n_keys); },
+        py::arg("trees_per_pass"), py::arg("NN"), py::arg("NB"), py::arg("n_keys"));
+  m.attr("QTREE_WEIGHT_MAX_KEYS") = (int)QTREE_WEIGHT_MAX_KEYS;
+  m.attr("QTREE_WEIGHT_MAX_TREES") = (int)QTREE_WEIGHT_MAX_TREES;
+  m.attr("QTREE_WEIGHT_SEG") = (int)QTREE_WEIGHT_SEG;
+  m.attr("QTREE_WEIGHT_DEFAULT_TPP") = (int)QTREE_WEIGHT_DEFAULT_TPP;
+  m.attr("QTREE_WEIGHT_MAX_TPP") = (int)QTREE_WEIGHT_MAX_TPP;
+  m.attr("QTREE_MAX_D") = (int)QTREE_MAX_D;
+  m.attr("QTREE_MAX_LEAVES") = (int)QTREE_MAX_LEAVES;
   m.attr("HIST_W") = (int)HIST_W;
   m.attr("SC_NSCAL") = (int)SC_NSCAL;
 }

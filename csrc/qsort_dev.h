@@ -1,4 +1,5 @@
-// Device helpers shared by the quantile-sort kernels (k_qsort.hip, k_qsort2.hip, k_qtree.hip): the
+// Device helpers shared by the quantile-sort kernels (k_qsort.hip, k_qsort2.hip, k_qtree.hip,
+// k_qtree_weight.hip): the
 // order-preserving float -> uint32 key map, the key load from the compacted panel and
 // (k_qtree.hip) the wave's step of the radix select.
 #pragma once
@@ -29,6 +30,24 @@ DLAP_DEV uint32_t qkey_load(const PanelView& a, bool is_char, int col, const flo
   }
   const int i = gp(a.rowti)[r].y;
   return qkey_u32(gp(ext)[i]);
+}
+
+// Full-width key of compact row r = (t, i) in key column c of a call (c < F: panel column c, else the
+// dense array c - F of extra [E][T][N]): qkey_u32 of the fp32 value, a bf16 characteristic widened
+// exactly first. Against qkey_u32 of a breakpoint this is the float comparison for any breakpoint
+// value. Its high half is qkey_load's bf16 key; the low half is 0xFFFF for a negative value where
+// qkey_load leaves 0, which is what the comparison with a full-width negative breakpoint needs
+// (k_qtree_weight.hip; the sort kernels compare 16-bit prefixes and keep qkey_load).
+template <bool F32>
+DLAP_DEV uint32_t qkey_row(const PanelView& a, int c, const float* extra, int t, int r, int i) {
+  float x;
+  if (c < a.F) {
+    if constexpr (F32) x = gp(reinterpret_cast<const float*>(a.X))[(size_t)r * a.KP + c];
+    else x = __uint_as_float((uint32_t)gp(reinterpret_cast<const u16*>(a.X))[(size_t)r * a.KP + c] << 16);
+  } else {
+    x = gp(extra)[((size_t)(c - a.F) * a.T + t) * a.N + i];
+  }
+  return qkey_u32(x);
 }
 
 // One wave's step of the multi-level radix select (k_qsort2.hip's scan): the histogram h of

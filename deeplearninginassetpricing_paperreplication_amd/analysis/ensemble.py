@@ -104,7 +104,8 @@ def evaluate_ensemble(checkpoint_dirs: Sequence[str], data_dir: str, device: str
                       knockout_macro: bool = False, knockout_macro_groups=None, knockout_macro_base="zero",
                       tree_sorts=None, tree_chars=None, tree_depth: int = 3, tree_splits=2,
                       tree_out: str = None, tree_prune: bool = False, prune_max_assets: int = 40,
-                      prune_grid="3x3x16", prune_out: str = None) -> Dict:
+                      prune_grid="3x3x16", prune_out: str = None, prune_metrics: bool = False,
+                      prune_weights_out: str = None) -> Dict:
     """Reference output and return value; ``paper=True`` (CLI ``--paper_metrics``) adds the
     paper's EV / XS-R² / turnover / max 1-month loss of the ensemble's SDF factor per split;
     ``importance=True`` (CLI ``--variable_importance``) adds the sensitivity ranking of the
@@ -165,11 +166,17 @@ def evaluate_ensemble(checkpoint_dirs: Sequence[str], data_dir: str, device: str
     on all three splits and prunes their nodes into a sparse mean-variance SDF (``analysis.tree_prune``:
     at most ``prune_max_assets`` nodes, ``prune_grid`` = ``N0xN2xN1`` penalties of ``l0 x l2 x l1``,
     selected on the validation split), printed next to the ensemble under the key ``tree_prune`` and
-    written to ``prune_out`` (JSON) when given."""
+    written to ``prune_out`` (JSON) when given. ``prune_metrics=True`` (CLI ``--prune_metrics``, with
+    ``tree_prune``) forms the stock-level weights of the pruned SDF (``tree_prune.pruned_weights``) and prints
+    its EV / XS-R2 / turnover / max 1-month loss on the test split, the Sharpe ratios recomputed from the
+    weights and the self-check ``max |sum_i w R - R_split . theta|``, under the key ``tree_prune_metrics`` (and
+    in ``prune_out``); ``prune_weights_out`` (``.npz``) saves the three dense weights."""
     say = print if verbose else (lambda *a, **k: None)
     bar = "=" * 70
     if tree_prune and not (tree_sorts or tree_chars):
         raise ValueError("tree_prune needs tree_sorts or tree_chars (CLI: --tree_prune with --tree_sorts / --tree_chars)")
+    if (prune_metrics or prune_weights_out) and not tree_prune:
+        raise ValueError("prune_metrics needs tree_prune (CLI: --prune_metrics with --tree_prune)")
     say(bar); say(f"ENSEMBLE EVALUATION ({len(checkpoint_dirs)} models, averaged weights)"); say(bar); say()
     datasets = load_splits(data_dir)
     batches = {s: d.get_full_batch() for s, d in zip(SPLITS, datasets)}
@@ -332,6 +339,7 @@ def evaluate_ensemble(checkpoint_dirs: Sequence[str], data_dir: str, device: str
             from . import tree_prune as tp
             n0, n2, n1 = tp.parse_prune_grid(prune_grid)
             by_split = {sort_split: res_ts}
+            ws_split = {sort_split: wavg}
             for s in SPLITS:
                 if s in by_split:
                     continue
@@ -341,6 +349,7 @@ def evaluate_ensemble(checkpoint_dirs: Sequence[str], data_dir: str, device: str
                     ws = average_weights([w[s] for w in weights], np_batches[s]["mask"])
                 by_split[s] = ts.tree_sorted_portfolios(models, batches[s], trees, splits=splits, device=device, names=names,
                                                         weights=ws)
+                ws_split[s] = ws
             pruned = tp.prune_trees(by_split, l0=tp.PRUNE_L0[:n0], l2_rel=tp.PRUNE_L2_REL[:n2], n1=n1,
                                     max_assets=prune_max_assets, device=device)
             out["tree_prune"] = pruned
@@ -352,9 +361,26 @@ def evaluate_ensemble(checkpoint_dirs: Sequence[str], data_dir: str, device: str
                                          key_names=kn):
                 say(line)
             say()
+            pmj = None
+            if prune_metrics or prune_weights_out:
+                pw = tp.pruned_weights(pruned, by_split, batches, models, device=device, weights=ws_split)
+                pmx = tp.pruned_metrics(pruned, by_split, pw, batches)
+                out["tree_prune_metrics"] = pmx
+                pmj = {k: float(v) for k, v in pmx.items()}
+                say(bar); say("PRUNED TREES: STOCK-LEVEL WEIGHTS (EV / XS-R2 / turnover / max 1-month loss, test split)")
+                say(bar); say()
+                for line in tp.format_pruned_metrics(pmx, gan=out["paper_metrics"]["test"] if paper else None):
+                    say(line)
+                say()
+                if prune_weights_out:
+                    np.savez(prune_weights_out, **{s: pw[s] for s in SPLITS})
+                    say(f"  Saved: {prune_weights_out}"); say()
             if prune_out:
+                pj = tp.pruned_to_json(pruned)
+                if pmj is not None:
+                    pj["tree_prune_metrics"] = pmj
                 with open(prune_out, "w") as fh:
-                    json.dump(tp.pruned_to_json(pruned), fh, indent=1)
+                    json.dump(pj, fh, indent=1)
                 say(f"  Saved: {prune_out}"); say()
     pred_json = {}
     if benchmark_ffn and not benchmarks:
@@ -522,6 +548,10 @@ def _parser():
     p.add_argument("--prune_max_assets", type=int, default=40, help="nodes of the pruned SDF at most")
     p.add_argument("--prune_grid", type=str, default="3x3x16", help="penalties N0xN2xN1 of l0 (<= 3) x l2 (<= 3) x l1")
     p.add_argument("--prune_out", type=str, default=None, help="write the pruning results to FILE.json")
+    p.add_argument("--prune_metrics", action="store_true",
+                   help="with --tree_prune: stock-level weights of the pruned SDF, its EV / XS-R2 / turnover / max loss")
+    p.add_argument("--prune_weights_out", type=str, default=None,
+                   help="with --prune_metrics: save the dense weights of the three splits to FILE.npz")
     p.add_argument("--benchmarks", action="store_true",
                    help="also evaluate the linear (LS) and elastic-net (EN) benchmark SDFs next to the ensemble")
     p.add_argument("--benchmark_grid", type=str, default="16x4", help="EN penalties: N1xN2 values of l1 x l2 (N2 <= 4)")
@@ -580,6 +610,12 @@ def _extra_kwargs(a) -> Dict:
         if not (a.tree_sorts or a.tree_chars):
             raise SystemExit("--tree_prune needs --tree_sorts or --tree_chars")
         kw.update(tree_prune=True, prune_max_assets=a.prune_max_assets, prune_grid=a.prune_grid, prune_out=a.prune_out)
+    if a.prune_metrics or a.prune_weights_out:
+        if not a.tree_prune:
+            raise SystemExit("--prune_metrics needs --tree_prune")
+        if not a.prune_metrics:
+            raise SystemExit("--prune_weights_out needs --prune_metrics")
+        kw.update(prune_metrics=True, prune_weights_out=a.prune_weights_out)
     if a.benchmarks:
         from .benchmarks import parse_grid
         kw.update(benchmarks=True, benchmark_grid=parse_grid(a.benchmark_grid), benchmark_center=a.benchmark_center,

@@ -26,9 +26,16 @@ at once, apply the lowest ``j`` with ``d != 0`` and go on from ``j + 1``. ``en_p
 kernel both do that, ``en_path_loop`` is the loop as written above; all three give the same bits.
 
 Limits: ``n <= 4096`` on the GPU (above it ``en_paths`` runs numpy and says so); finite inputs,
-``l1, l2 >= 0``. Out of scope: stock-level weights of the pruned SDF (and so EV / XS-R2 rows for it),
-LARS, cross-validation folds, the elastic net of ``analysis.benchmarks`` through the kernel, plots,
-multi-rank runs.
+``l1, l2 >= 0``.
+
+Stock-level weights. A node is an equally weighted basket, so the pruned SDF ``F_t = R_t . theta`` is
+a weight per stock-month: ``node_coefficients`` scatters ``theta`` (times ``node_returns``' depth factor)
+to the nodes, ``pruned_weights`` walks every stock down the selected trees (``tree_sorts.tree_weights``,
+``csrc/k_qtree_weight.hip`` on the GPU) and returns the dense ``w`` [T][N] with ``sum_i w R = F_t``, which
+``portfolio.paper_metrics`` and the pricing functions take like any other model's weight.
+
+Out of scope: value weighting, LARS, cross-validation folds, the elastic net of ``analysis.benchmarks``
+through the kernel, plots, multi-rank runs.
 """
 from __future__ import annotations
 
@@ -382,6 +389,80 @@ def prune_trees(res_by_split: Dict, l0=PRUNE_L0, l2_rel=PRUNE_L2_REL, n1: int = 
         if key in sol:
             out[key] = sol[key]
     return out
+
+
+# ---- stock-level weights of the pruned SDF ---------------------------------------------------------
+def node_coefficients(pr: Dict, res: Dict) -> np.ndarray:
+    """``coef`` float64 [P][NN] of the pruned SDF ``pr`` on the trees of ``res``: ``theta[u] * (1 /
+    sqrt(nodes_per_level[level_u]))`` (``node_returns``' own factor, one product; the factor is 1 without
+    ``depth_weight``) at the representative (tree, node) of the distinct node ``u``, 0 everywhere else."""
+    un = ts.unique_nodes(res["trees"], res["splits"])
+    theta = np.asarray(pr["theta"], dtype=np.float64)
+    if theta.shape != (len(un["nodes"]),):
+        raise ValueError(f"tree prune: theta has {theta.shape} entries, the trees have {len(un['nodes'])} distinct nodes")
+    lay = ts.tree_layout(res["splits"])
+    fac = np.ones(theta.shape[0], np.float64)
+    if pr.get("depth_weight", True):
+        npl = np.asarray(lay["nodes_per_level"], dtype=np.float64)
+        fac = 1.0 / np.sqrt(npl[np.asarray(un["levels"])])
+    coef = np.zeros((len(res["trees"]), lay["nodes"]), np.float64)
+    pi, ni = np.array([p for p, _ in un["nodes"]]), np.array([j for _, j in un["nodes"]])
+    coef[pi, ni] = theta * fac
+    return coef
+
+
+def pruned_weights(pr: Dict, res_by_split: Dict, batches: Dict, models: Sequence, device: str = "cpu",
+                   precision: str = "bf16", weights: Optional[Dict] = None) -> Dict:
+    """The dense stock-level weight ``w`` float32 [T][N] (0 at the invalid cells) of the pruned SDF per
+    split of ``res_by_split`` (``tree_sorted_portfolios`` results with their ``breaks``), on ``batches[split]``.
+    By construction ``sum_i w[t, i] R[t, i] = R_split[t] . theta`` up to rounding; an empty node contributes
+    a return of 0 and no stock weight. ``weights``: the ensemble weight per split, for trees that sort on
+    it. ``device`` and ``precision`` have to be those of the sorts: the walk needs the sort's own keys."""
+    out = {}
+    for s, res in res_by_split.items():
+        coef = node_coefficients(pr, res)
+        out[s] = ts.tree_weights(models, batches[s], res, coef, device=device, precision=precision,
+                                 weights=None if weights is None else weights.get(s))["w"]
+    return out
+
+
+def factor_from_weights(w: np.ndarray, returns, mask) -> np.ndarray:
+    """``F[t] = sum_i w[t, i] R[t, i]`` over the valid cells in float64."""
+    m = _host(mask, bool)
+    return (np.asarray(w, dtype=np.float64) * _host(returns, np.float64) * m).sum(axis=1)
+
+
+def pruned_metrics(pr: Dict, res_by_split: Dict, w_by_split: Dict, batches: Dict) -> Dict:
+    """The paper's rows of the pruned SDF from its stock-level weights: ``paper_metrics`` of the test
+    split on ``-w`` (that function's factor is ``-w . R``, the ensemble's sign), the three Sharpe ratios of
+    ``sum_i w R`` and ``self_check``, the largest ``|sum_i w R - R_split . theta|`` over all periods."""
+    from .portfolio import paper_metrics
+    out, worst = {}, 0.0
+    theta = np.asarray(pr["theta"], dtype=np.float64)
+    for s in SPLITS:
+        b = batches[s]
+        f = factor_from_weights(w_by_split[s], b["returns"], b["mask"])
+        ref = node_returns(res_by_split[s], pr.get("depth_weight", True))[0] @ theta
+        worst = max(worst, float(np.abs(f - ref).max()) if f.size else 0.0)
+        out[s + "_sharpe"] = sharpe_ddof0(f)
+    tb = batches["test"]
+    pm = paper_metrics(-np.asarray(w_by_split["test"], dtype=np.float32), _host(tb["returns"], np.float32), _host(tb["mask"], bool))
+    out.update({k: pm[k] for k in ("ev", "xs_r2", "turnover", "max_1m_loss_std")})
+    out["self_check"] = worst
+    return out
+
+
+def format_pruned_metrics(pm: Dict, gan: Optional[Dict] = None) -> List[str]:
+    """The printed block of ``pruned_metrics`` (next to the ensemble's ``paper_metrics`` of the test split
+    when the run has them)."""
+    lines = [f"  {'':14s} {'EV':>8s} {'XS-R2':>8s} {'turnover':>9s} {'max 1m loss':>12s}",
+             f"  {'Pruned trees':14s} {pm['ev']:8.4f} {pm['xs_r2']:8.4f} {pm['turnover']:9.3f} {pm['max_1m_loss_std']:9.2f} sd"]
+    if gan is not None:
+        lines.append(f"  {'Ensemble':14s} {gan['ev']:8.4f} {gan['xs_r2']:8.4f} {gan['turnover']:9.3f} {gan['max_1m_loss_std']:9.2f} sd")
+    lines.append(f"  Sharpe from the stock-level weights:  train {pm['train_sharpe']:8.4f}  valid {pm['valid_sharpe']:8.4f}  "
+                 f"test {pm['test_sharpe']:8.4f}")
+    lines.append(f"  Self-check max |sum_i w R - R_split . theta| over all periods: {pm['self_check']:.3e}")
+    return lines
 
 
 def format_pruned(pr: Dict, gan: Optional[Dict] = None, key_names: Optional[Sequence] = None) -> List[str]:

@@ -26,7 +26,11 @@ Per (period, tree, node) the raw result holds the row count and the float64 sums
 columns (the return, then the ensemble weight); per (period, tree) ``breaks`` [NB].
 
 Pruning the nodes into an SDF (the elastic-net mean-variance step of the tree paper) is
-``analysis.tree_prune``. Out of scope: sharing selects between trees with a common prefix, an independent (non-nested) mode, value
+``analysis.tree_prune``. A combination of nodes is also a weight per stock-month, since a node is an
+equally weighted basket: ``tree_weights_numpy`` is its definition, ``tree_weights`` runs it on the CPU or
+through ``Engine.tree_weights`` / ``csrc/k_qtree_weight.hip`` with the same bits.
+
+Out of scope: sharing selects between trees with a common prefix, an independent (non-nested) mode, value
 weighting beyond a caller's value column, more than 36 leaves, plots.
 """
 from __future__ import annotations
@@ -304,6 +308,196 @@ def tree_sorted_portfolios(models: Sequence, batch: Dict, trees: Sequence, split
            "level_offsets": list(lay["level_offsets"]), "break_offsets": list(lay["break_offsets"])}
     if "gpu_ms" in raw:
         out["gpu_ms"] = raw["gpu_ms"]
+    return out
+
+
+# ---- stock-level weights of a combination of nodes ---------------------------------------------------
+MAX_WEIGHT_KEYS = 32      # distinct key columns of a GPU call (QTREE_WEIGHT_MAX_KEYS of csrc/qtree_weight.h)
+
+
+def _check_coef(coef, P: int, NN: int) -> np.ndarray:
+    coef = np.ascontiguousarray(np.asarray(coef), dtype=np.float64)
+    if coef.shape != (P, NN):
+        raise ValueError(f"tree weights: coef must be [{P}][{NN}] (trees x nodes), got {list(coef.shape)}")
+    if not np.isfinite(coef).all():
+        raise ValueError("tree weights: coef must be finite")
+    return coef
+
+
+def active_keys(trees: Sequence, splits, coef: np.ndarray) -> List[int]:
+    """The distinct key columns a weight pass reads: those of the levels ``1 .. deepest level with a
+    non-zero coefficient`` of every tree, in the order of first use."""
+    off = tree_layout(splits)["level_offsets"]
+    out: List[int] = []
+    for p, tr in enumerate(trees):
+        lv = [l for l in range(len(off) - 1) if np.any(np.asarray(coef)[p, off[l]:off[l + 1]] != 0)]
+        for c in tr[:max(lv) if lv else 0]:
+            if c not in out:
+                out.append(int(c))
+    return out
+
+
+def _active_depths(splits, coef: np.ndarray) -> List[int]:
+    """Per tree the deepest level with a non-zero coefficient (-1: none)."""
+    off = tree_layout(splits)["level_offsets"]
+    return [max([l for l in range(len(off) - 1) if np.any(coef[p, off[l]:off[l + 1]] != 0)], default=-1)
+            for p in range(coef.shape[0])]
+
+
+def tree_weights_numpy(keys: np.ndarray, trees: Sequence, mask: np.ndarray, splits, breaks: np.ndarray, count: np.ndarray,
+                       coef: np.ndarray, dtype=np.float32) -> np.ndarray:
+    """The stock-level weight of a combination of tree nodes: the definition in numpy. A node is an
+    equally weighted basket, so ``coef`` float64 [P][NN] (finite, ``-0.0`` read as 0) over the nodes of
+    the ``P`` trees is a weight per stock-month. ``keys`` [T][N][P'], ``trees``, ``mask``, ``splits`` as for
+    ``tree_sort_numpy``; ``breaks`` [T][P][NB] and ``count`` [T][P][NN] of a tree sort of these keys.
+
+    A valid row ``(t, i)`` follows the sort's rule down every tree, ``node_0 = 0``, ``node_l = node_{l-1} Q_l +
+    #{d : key_{c_l} + 0 > b_{node_{l-1}, d}}`` (a comparison with a NaN breakpoint is false), and collects ::
+
+        acc = +0.0 (float64)
+        for p ascending, for l = 0 .. D ascending, j = level_offsets[l] + node_l:
+            if coef[p][j] != 0:  acc = acc + coef[p][j] / count[t][p][j]      one division, one addition
+        w[t, i] = dtype(acc)
+
+    Returns ``w`` [T][N] in ``dtype`` (float32, or float64 for the unrounded ``acc``), 0 at the invalid
+    cells. A visited node with a non-zero coefficient and ``count == 0`` means the breakpoints are not
+    those of these keys: ``ValueError``."""
+    lay = tree_layout(splits)
+    qs, D, off, boff, nl = lay["splits"], lay["depth"], lay["level_offsets"], lay["break_offsets"], lay["nodes_per_level"]
+    keys = np.asarray(keys)
+    mask = np.asarray(mask).astype(bool)
+    T, N, PK = keys.shape
+    trees = _check_trees(trees, D, PK)
+    P = len(trees)
+    breaks, count = np.asarray(breaks), np.asarray(count)
+    if breaks.shape != (T, P, lay["breaks"]) or count.shape != (T, P, lay["nodes"]):
+        raise ValueError("tree weights: breaks must be [T][P][NB] and count [T][P][NN] of a tree sort of these trees")
+    coef = _check_coef(coef, P, lay["nodes"])
+    if np.dtype(dtype) not in (np.dtype(np.float32), np.dtype(np.float64)):
+        raise ValueError("tree weights: dtype must be float32 or float64")
+    zero = keys.dtype.type(0)
+    depth = _active_depths(splits, coef)
+    out = np.zeros((T, N), np.float64)
+    for t in range(T):
+        idx = np.nonzero(mask[t])[0]
+        n = int(idx.size)
+        if n == 0:
+            continue
+        acc = np.zeros(n, np.float64)
+        for p, tr in enumerate(trees):
+            node = np.zeros(n, np.int64)
+            for l in range(depth[p] + 1):           # (the levels below add nothing: their coefficients are 0)
+                if l >= 1:
+                    Q = qs[l - 1]
+                    k = keys[t, idx, tr[l - 1]] + zero                  # (-0.0 + 0.0 = +0.0)
+                    b = breaks[t, p, boff[l - 1]:boff[l]].reshape(nl[l - 1], Q - 1)
+                    node = node * Q + (k[:, None] > b[node]).sum(axis=1)
+                c = coef[p, off[l] + node]
+                nz = c != 0
+                if nz.any():
+                    m = count[t, p, off[l] + node[nz]]
+                    if (m <= 0).any():
+                        raise ValueError(f"tree weights: a row of period {t} reaches an empty node of tree {p} (level {l}): "
+                                         "the breakpoints are not those of these keys")
+                    acc[nz] = acc[nz] + c[nz] / m.astype(np.float64)
+        out[t, idx] = acc
+    return out.astype(dtype)
+
+
+def _gpu_tree_weights(spec, batch, w: Optional[torch.Tensor], trees, splits, breaks, count, coef, precision: str,
+                      want_acc: bool, trees_per_pass: Optional[int]) -> Dict:
+    from ..engine.runner import GANEngine
+    eng = GANEngine(spec, 1, max_epochs=4, precision=precision)
+    eng.set_data(batch)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    T, N = batch["mask"].shape
+    w_out = torch.zeros((T, N), dtype=torch.float32, device=dev)
+    acc_out = torch.zeros((T, N), dtype=torch.float64, device=dev) if want_acc else None
+    torch.cuda.synchronize(dev)
+    try:
+        # a level below a tree's deepest non-zero one is never read: its key is handed over as column 0, so
+        # that a tree that names the weight only there needs no extra key
+        depth = _active_depths(splits, coef)
+        trees = [[c if l < depth[p] else 0 for l, c in enumerate(tr)] for p, tr in enumerate(trees)]
+        r = eng.eng.tree_weights(0, trees, list(splits), np.ascontiguousarray(breaks, dtype=np.float32),
+                                 np.ascontiguousarray(count, dtype=np.int32), coef, 0 if w is None else w.data_ptr(),
+                                 0 if w is None else 1, w_out.data_ptr(), 0 if acc_out is None else acc_out.data_ptr(),
+                                 int(trees_per_pass or 0))
+    finally:
+        eng.eng.sync()
+    out = {"w": w_out.cpu().numpy(), "gpu_ms": float(r["gpu_ms"]), "active_trees": int(r["active_trees"]),
+           "passes": int(r["passes"])}
+    if acc_out is not None:
+        out["acc"] = acc_out.cpu().numpy()
+    return out
+
+
+def tree_weights(models: Sequence, batch: Dict, res: Dict, coef: np.ndarray, device: str = "cpu",
+                 names: Optional[Sequence] = None, weights: Optional[np.ndarray] = None, precision: str = "bf16",
+                 acc: bool = False, trees_per_pass: Optional[int] = None) -> Dict:
+    """The stock-level weight of ``sum_nodes coef[p][j] x (node (p, j) of res)``: ``res`` a
+    ``tree_sorted_portfolios`` result of ``batch`` (its ``trees``, ``splits``, ``breaks`` and ``count`` are read),
+    ``coef`` float64 [P][NN]. On the CPU it is ``tree_weights_numpy`` on the float32 keys; on the GPU
+    ``Engine.tree_weights`` (``csrc/k_qtree_weight.hip``) on an engine built as the sort's, with the
+    ensemble weight as the one extra key when a level that is read uses ``weight`` (a tree's levels below
+    its deepest non-zero coefficient are not read, and a tree that names ``weight`` only there needs none).
+    ``models``, ``weights`` and ``precision`` as for ``tree_sorted_portfolios`` (neither is needed on the CPU when
+    no level that is read uses the weight). Outside ``qtree_weight_supported`` the GPU call runs numpy on the
+    keys the engine would hold (characteristics rounded to bf16 for ``precision="bf16"``) and says so.
+
+    Returns ``w`` float32 [T][N] (0 at the invalid cells), with ``acc=True`` also ``acc`` float64, and from
+    the kernel ``gpu_ms``, ``active_trees`` and ``passes``. No output bit depends on ``trees_per_pass``."""
+    models = list(models)
+    mask = batch["mask"].bool()
+    T, N, F = batch["individual_features"].shape
+    lay = tree_layout(res["splits"])
+    trs = _check_trees(_resolve_trees(res["trees"], F, names), lay["depth"], F + 1)
+    coef = _check_coef(coef, len(trs), lay["nodes"])
+    breaks, count = np.asarray(res["breaks"]), np.asarray(res["count"])
+    used = active_keys(trs, lay["splits"], coef)
+    need_w = F in used
+    gpu = str(device).startswith("cuda")
+    engine_keys = False                                          # numpy on the keys an engine of ``precision`` holds
+    if gpu:
+        from ..ops import native
+        nat = native.load(required=False)
+        if nat is None:
+            print("[tree_weights] native extension not available: using the CPU path")
+            gpu = False
+        elif not nat.qtree_weight_supported(list(lay["splits"]), len(trs), int(T), len(used)):
+            print(f"[tree_weights] {len(used)} distinct keys, {len(trs)} trees, {int(T)} periods are outside "
+                  f"qtree_weight_supported (at most {nat.QTREE_WEIGHT_MAX_KEYS} keys, {nat.QTREE_WEIGHT_MAX_TREES} trees, "
+                  "65535 periods): using the numpy path")
+            gpu, engine_keys = False, True
+    if not models and (gpu or (need_w and weights is None)):     # (the engine is built from a model's spec)
+        raise ValueError("no models")
+    if gpu:
+        dev = torch.device("cuda", torch.cuda.current_device())
+        w = None
+        if need_w:
+            w = (sp._gpu_weights(models, batch) if weights is None
+                 else torch.as_tensor(np.asarray(weights, dtype=np.float32)).to(dev).contiguous())
+        out = _gpu_tree_weights(models[0].spec, batch, w, trs, lay["splits"], breaks, count, coef, precision, acc,
+                                trees_per_pass)
+        if not np.isfinite(out["w"]).all():
+            raise ValueError("tree weights: a row reaches an empty node with a non-zero coefficient (or the weight leaves "
+                             "float32): the breakpoints are not those of these keys")
+        return out
+    cpu = {k: (v.cpu() if isinstance(v, torch.Tensor) else v) for k, v in batch.items()}
+    feats = cpu["individual_features"]
+    if engine_keys and precision == "bf16":                      # (res was sorted on the engine's bf16 panel)
+        feats = feats.to(torch.bfloat16).to(torch.float32)
+    keys = feats.numpy().astype(np.float32)
+    if need_w:
+        w = sp._cpu_weights(models, cpu) if weights is None else np.asarray(weights)
+        wk = w.astype(np.float32)[:, :, None]
+    else:
+        wk = np.zeros((T, N, 1), np.float32)
+    keys = np.concatenate([keys, wk], axis=2)
+    a64 = tree_weights_numpy(keys, trs, mask.cpu().numpy(), lay["splits"], breaks, count, coef, dtype=np.float64)
+    out = {"w": a64.astype(np.float32)}
+    if acc:
+        out["acc"] = a64
     return out
 
 

@@ -76,7 +76,9 @@ def variant_path(variant: str) -> Path:
 # without accumulator-file moves); its long-lived weight-gradient sums are pinned to AGPRs by asm.
 # k_encd.hip: bit-exact fp64 against the numpy definition, so no multiply-add is contracted into an fma
 # (__dmul_rn / __dadd_rn and a file-scope pragma do not stop hipcc's default contraction, the flag does).
-FILE_FLAGS: dict = {"k_tbwd.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "k_encd.hip": ["-ffp-contract=off"]}
+# k_qtree_weight.hip: the same for its fp64 acc chain (divisions and additions only; the flag keeps it so).
+FILE_FLAGS: dict = {"k_tbwd.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "k_encd.hip": ["-ffp-contract=off"],
+                    "k_qtree_weight.hip": ["-ffp-contract=off"]}
 
 
 def build(force: bool = False, jobs: int = 8, verbose: bool = True, ubsan: bool = False,
